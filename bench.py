@@ -1,8 +1,12 @@
 #!/usr/bin/env python
 """Benchmark: agent-steps/s of the fused HIP swarm step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR also writes what the last
+timed step returned (obs, rew, done, term_obs) as DIR/<name>.npy (float32); the same arguments give the same
+inputs, so two builds can be compared output for output.  --full adds every other leg listed below.
 
 `python bench.py --gpus N` (N > 1) with no launcher around starts the second form itself as a child process
 (before any HIP call) and relays rank 0's line; under a launcher WORLD_SIZE must equal --gpus (else exit 1).
@@ -15,6 +19,9 @@ collective on the data path; value = all ranks' agent-steps / max-over-ranks wal
 
 Besides the required fields the JSON line carries:
   roofline      algorithmic bytes per launch / HIP-event kernel time vs 8 TB/s
+and with --full (null in a plain run):
+  window, roofline.kernel_us_eager_single, nonfinite_guard    the timed region's fixed cost, one eager launch
+                bracketed by its own events, the step's non-finite counters: runs and read-backs after the timed steps
   cpu_baseline  the C oracle (oracle/, OpenMP over envs) on this host, bounded ~10 s sample
   end_to_end    SURVEY §8 d(ii): PPO agent-steps/s of the GPU trainer (quadswarm_amd/ppo.py) --
                 rollout over the same env shard + HIP GAE + minibatch update with one RCCL all-reduce
@@ -509,6 +516,18 @@ def raw_streams(torch, dev, n, spare):
     return streams, destroy
 
 
+def dump_outputs(path, envs):
+    """What the last step returned to its caller -- obs [I, obs_dim], rew [I], done [I], term_obs [I, obs_dim] of
+    every handle in `envs` (the env blocks in drone order) -- as path/<name>.npy, float32.  A C3 shard is 14 MB; the
+    largest config stays under 64 MB."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name in ("obs", "rew", "done", "term_obs"):
+        a = torch.cat([getattr(e, name) for e in envs]).to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -582,10 +601,18 @@ def main(argv=None):
     ap.add_argument("--no-episode-stats", action="store_true",
                     help="A/B only: skip the episode_extra_stats accumulators the reference's step keeps")
     ap.add_argument("--quads-mode", default=None, help="A/B only: override the config's quads_mode (goal scenario)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (obs, rew, done, term_obs of this "
+                         "rank's shard) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true", default=os.environ.get("QS_BENCH_FULL") == "1",
+                    help="after the timed steps also run the secondary legs: window, eager single launch, non-finite "
+                         "guard, cpu_baseline, end_to_end (a plain run only times the steps); QS_BENCH_FULL=1 in the "
+                         "environment does the same for a wrapper script")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="seconds per cpu_baseline leg (3 legs)")
     ap.add_argument("--cpu-worker", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--e2e-iters", type=int, default=2, help="timed PPO iterations for end_to_end (0 = skip)")
+    ap.add_argument("--e2e-iters", type=int, default=2,
+                    help="with --full: timed PPO iterations for end_to_end (0 = skip)")
     ap.add_argument("--e2e-steps", type=int, default=0, help="override the PPO rollout length n_steps")
     ap.add_argument("--e2e-unfused", action="store_true",
                     help="A/B only: the rollout evaluates the torch policy module instead of the fused encoders")
@@ -711,39 +738,44 @@ def main(argv=None):
     if world > 1:
         dist.barrier()
     total_agent_steps, el, per_rank = aggregate_ranks(I * args.steps, el, world, dev)
+    if args.dump_outputs:   # before anything else steps the envs again
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                     [e for e, _, _ in run.entries])
 
-    # the timed region's fixed cost, measured after it (untimed): the same event records and synchronize with no
-    # step between them (median of 5) -- the wall the region pays whatever the kernel time
-    empties = []
-    for _ in range(5):
-        e0_, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize(dev)
-        t0_ = time.perf_counter()
-        e0_.record(stream)
-        e1_.record(stream)
-        torch.cuda.synchronize(dev)
-        empties.append(((time.perf_counter() - t0_) * 1e6, e0_.elapsed_time(e1_) * 1e3))
-    empty_wall, empty_ev = sorted(empties)[2]
-    window = {"region_wall_us": round(el * 1e6, 2), "region_events_us": round(k_ms * args.steps * 1e3, 2),
-              "host_side_us": round(el * 1e6 - k_ms * args.steps * 1e3, 2),
-              "empty_region_wall_us": round(empty_wall, 2), "empty_region_events_us": round(empty_ev, 2),
-              "note": "region wall = region events (graph launch latency + the step kernels) + host side (event "
-                      "records, synchronize wake-up); tools/window_probe.py and profiles/r06/window_* split it "
-                      "per launch"}
+    window = k_eager_ms = guard = None
+    if args.full:
+        # the timed region's fixed cost, measured after it (untimed): the same event records and synchronize with no
+        # step between them (median of 5) -- the wall the region pays whatever the kernel time
+        empties = []
+        for _ in range(5):
+            e0_, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(dev)
+            t0_ = time.perf_counter()
+            e0_.record(stream)
+            e1_.record(stream)
+            torch.cuda.synchronize(dev)
+            empties.append(((time.perf_counter() - t0_) * 1e6, e0_.elapsed_time(e1_) * 1e3))
+        empty_wall, empty_ev = sorted(empties)[2]
+        window = {"region_wall_us": round(el * 1e6, 2), "region_events_us": round(k_ms * args.steps * 1e3, 2),
+                  "host_side_us": round(el * 1e6 - k_ms * args.steps * 1e3, 2),
+                  "empty_region_wall_us": round(empty_wall, 2), "empty_region_events_us": round(empty_ev, 2),
+                  "note": "region wall = region events (graph launch latency + the step kernels) + host side (event "
+                          "records, synchronize wake-up); tools/window_probe.py and profiles/r06/window_* split it "
+                          "per launch"}
 
-    # secondary: one eager launch of the one handle bracketed by its own events (includes the host launch gap)
-    nk = min(200, max(20, args.steps // 10))
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nk)]
-    for s_ev, e_ev in evs:
-        s_ev.record(stream)
-        env.step(actions)
-        e_ev.record(stream)
-    torch.cuda.synchronize(dev)
-    k_eager_ms = sum(s.elapsed_time(e) for s, e in evs) / nk
-    guard = env.counters()
+        # secondary: one eager launch of the one handle bracketed by its own events (includes the host launch gap)
+        nk = min(200, max(20, args.steps // 10))
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nk)]
+        for s_ev, e_ev in evs:
+            s_ev.record(stream)
+            env.step(actions)
+            e_ev.record(stream)
+        torch.cuda.synchronize(dev)
+        k_eager_ms = sum(s.elapsed_time(e) for s, e in evs) / nk
+        guard = env.counters()
 
     e2e = None
-    if args.e2e_iters > 0:
+    if args.full and args.e2e_iters > 0:
         log = (lambda m: print(m, file=sys.stderr, flush=True)) if rank == 0 else None
         try:
             e2e = end_to_end(env, cfg, dev, world, args.e2e_iters, args.e2e_steps or None, log,
@@ -804,7 +836,7 @@ def main(argv=None):
                          + (f" (one step = {S} concurrent launches of {cfg.num_envs // S} envs; achieved = bytes per"
                             " step / step time, the aggregate rate of the overlapping launches)" if S > 1 else ""),
                          "launches_per_step": S,
-                         "kernel_us_eager_single": round(k_eager_ms * 1e3, 3),
+                         "kernel_us_eager_single": None if k_eager_ms is None else round(k_eager_ms * 1e3, 3),
                          "bytes_per_agent_step": round(bpa, 1),
                          "bytes_per_agent_step_state_complete": (round(state_bytes_per_agent_step(cfg)[0], 1)
                                                                  if cfg.flavor == "B" else None),
@@ -822,7 +854,7 @@ def main(argv=None):
             "cpu_baseline": None,
             "end_to_end": e2e,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.config, seconds=args.cpu_seconds)
             except Exception as e:  # never let the baseline leg kill the GPU number

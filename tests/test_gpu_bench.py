@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_driver_arguments_replay_graphs():
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5",
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full",
                         "--no-cpu-baseline", "--e2e-iters", "0"], cwd=ROOT, capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -33,6 +33,30 @@ def test_bench_driver_arguments_replay_graphs():
     assert line["ms_per_step"] * 1e3 >= 0.95 * rf["kernel_us"]
     assert abs(line["value"] - 32768 / (line["ms_per_step"] * 1e-3)) <= 0.01 * line["value"]
     assert line["nonfinite_guard"] == {"nonfinite_obs": 0, "nonfinite_rew": 0, "nonfinite_state": 0}
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_outputs(tmp_path):
+    """Without --full the line keeps the headline fields and leaves the secondary legs null; --dump-outputs writes
+    the last timed step's obs / rew / done / term_obs as float32 .npy files of the shard's shape."""
+    import numpy as np
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 7 and line["warmup"] == 3 and line["unit"] == "agent-steps/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True and line["ms_per_step"] > 0
+    assert abs(line["value"] - 32768 / (line["ms_per_step"] * 1e-3)) <= 0.01 * line["value"]
+    assert line["config"]["launch"].startswith("1 hipGraph replays")
+    for k in ("window", "nonfinite_guard", "cpu_baseline", "end_to_end"):
+        assert line[k] is None, k
+    od = line["config"]["obs_dim"]
+    want = {"obs": (32768, od), "rew": (32768,), "done": (32768,), "term_obs": (32768, od)}
+    for name, shape in want.items():
+        a = np.load(tmp_path / (name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), name
+    assert np.abs(np.load(tmp_path / "obs.npy")).max() > 0
+    assert set(np.unique(np.load(tmp_path / "done.npy"))) <= {0.0, 1.0}
 
 
 @pytest.mark.gpu

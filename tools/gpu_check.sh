@@ -24,7 +24,7 @@ for s in "$@"; do
     testsall) step gpu_tests 900 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread ;;
     testsnew) step gpu_tests_new 600 python -u -m pytest tests/test_gpu_stats.py tests/test_gpu_guard_params.py tests/test_gpu_c5.py -v --timeout 200 --timeout-method thread ;;
     testspar) step gpu_tests_par 900 python -u -m pytest tests/test_gpu_stats.py tests/test_gpu_parity.py tests/test_gpu_parity_a.py -v --timeout 300 --timeout-method thread ;;
-    benchdrv) step bench_driver 600 python bench.py --gpus 1 --steps 20 --warmup 5 ;;
+    benchdrv) step bench_driver 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full ;;
     benchwarm)
       step bw_20_5 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --e2e-iters 0
       step bw_20_500 200 python bench.py --steps 20 --warmup 500 --no-cpu-baseline --e2e-iters 0
@@ -41,7 +41,7 @@ for s in "$@"; do
       python tools/kt_summary.py gpurun_out/kt_on gpurun_out/kt_off > gpurun_out/kt_summary.txt 2>&1
       rm -f gpurun_out/kt_*/*/*kernel_trace.csv gpurun_out/kt_*/*kernel_trace.csv
       ;;
-    benchn64) step bench_n64 300 python bench.py --config n64 --steps 1000 --cpu-seconds 5 --e2e-iters 0 ;;
+    benchn64) step bench_n64 300 python bench.py --config n64 --steps 1000 --full --cpu-seconds 5 --e2e-iters 0 ;;
     abstatsa)
       step a8_nost 300 python bench.py --config a8 --steps 1000 --no-cpu-baseline --e2e-iters 0 --no-episode-stats
       CONFIG=a8 STEPS=1000 step a8_ab 600 bash tools/ab_jit.sh base: nocol:-DQS_DIAG_A_NOCOL
@@ -52,30 +52,30 @@ for s in "$@"; do
       ;;
     par64) step gpu_tests_64 600 python -u -m pytest tests/test_gpu_parity.py -v -k "64" --timeout 300 --timeout-method thread ;;
     benchblocks) step bench_blocks 600 python bench.py --steps 2000 --streams 4 --no-cpu-baseline --e2e-iters 0 ;;
-    bench) step bench 600 python bench.py ;;
+    bench) step bench 600 python bench.py --full ;;
     ppotests) step ppo_tests 600 python -m pytest tests/test_gpu_ppo.py -q -x ;;
-    e2ea) step e2e_a8 600 python bench.py --config a8 --steps 500 --no-cpu-baseline --e2e-iters 1 --e2e-steps 64 ;;
+    e2ea) step e2e_a8 600 python bench.py --config a8 --steps 500 --full --no-cpu-baseline --e2e-iters 1 --e2e-steps 64 ;;
     e2ec3p)    # C3 end to end, the rollout encoders in fp32 and split-f16 (x3)
-      step e2e_c3_fp32 600 python bench.py --config c3 --steps 500 --no-cpu-baseline --e2e-iters 2 --e2e-precision fp32
-      step e2e_c3_x3 600 python bench.py --config c3 --steps 500 --no-cpu-baseline --e2e-iters 2 --e2e-precision x3
+      step e2e_c3_fp32 600 python bench.py --config c3 --steps 500 --full --no-cpu-baseline --e2e-iters 2 --e2e-precision fp32
+      step e2e_c3_x3 600 python bench.py --config c3 --steps 500 --full --no-cpu-baseline --e2e-iters 2 --e2e-precision x3
       ;;
     polt) step pol_tests 600 python -u -m pytest tests/test_gpu_policy_fused.py tests/test_gpu_ppo.py tests/test_gpu_trainer.py -x -v --timeout 200 --timeout-method thread ;;
-    e2ec3) step e2e_c3 600 python bench.py --config c3 --steps 500 --no-cpu-baseline --e2e-iters 1 ;;
-    e2ea512) step e2e_a8_512 900 python bench.py --config a8 --steps 500 --no-cpu-baseline --e2e-iters 2 ;;
+    e2ec3) step e2e_c3 600 python bench.py --config c3 --steps 500 --full --no-cpu-baseline --e2e-iters 1 ;;
+    e2ea512) step e2e_a8_512 900 python bench.py --config a8 --steps 500 --full --no-cpu-baseline --e2e-iters 2 ;;
     benchgen) step bench_generic 300 python bench.py --generic --steps 2000 --e2e-iters 0 --no-cpu-baseline ;;
     benchspec) step bench_spec 300 python bench.py --steps 2000 --e2e-iters 0 --no-cpu-baseline ;;
-    benchc2) step bench_c2 400 python bench.py --config c2 --steps 2000 --cpu-seconds 10 --e2e-iters 1 ;;
-    benchc5) step bench_c5 400 python bench.py --config c5 --steps 1000 --cpu-seconds 10 --e2e-iters 1 ;;
-    e2ea8) step e2e_a8_full 900 python bench.py --config a8 --steps 500 --no-cpu-baseline --e2e-iters 1 ;;
-    benchfast) step bench 300 python bench.py --steps 1000 --cpu-seconds 5 ;;
-    bencha) step bench_a8 400 python bench.py --config a8 --steps 1000 --cpu-seconds 10 --e2e-iters 0 ;;
-    bencha4) step bench_a4 400 python bench.py --config a4 --steps 1000 --cpu-seconds 5 ;;
-    benchc4) step bench_c4 400 python bench.py --config c4 --steps 1000 --cpu-seconds 10 --e2e-iters 0 ;;
-    benchc3) step bench_c3 400 python bench.py --config c3 --steps 2000 --cpu-seconds 10 ;;
+    benchc2) step bench_c2 400 python bench.py --config c2 --steps 2000 --full --cpu-seconds 10 --e2e-iters 1 ;;
+    benchc5) step bench_c5 400 python bench.py --config c5 --steps 1000 --full --cpu-seconds 10 --e2e-iters 1 ;;
+    e2ea8) step e2e_a8_full 900 python bench.py --config a8 --steps 500 --full --no-cpu-baseline --e2e-iters 1 ;;
+    benchfast) step bench 300 python bench.py --steps 1000 --full --cpu-seconds 5 ;;
+    bencha) step bench_a8 400 python bench.py --config a8 --steps 1000 --full --cpu-seconds 10 --e2e-iters 0 ;;
+    bencha4) step bench_a4 400 python bench.py --config a4 --steps 1000 --full --cpu-seconds 5 ;;
+    benchc4) step bench_c4 400 python bench.py --config c4 --steps 1000 --full --cpu-seconds 10 --e2e-iters 0 ;;
+    benchc3) step bench_c3 400 python bench.py --config c3 --steps 2000 --full --cpu-seconds 10 ;;
     replay) step gpu_replay 600 python -u -m pytest tests/test_gpu_replay.py tests/test_gpu_parity.py -x -v --timeout 300 --timeout-method thread ;;
-    benchmixr) step bench_c3mixr 400 python bench.py --config c3mixr --steps 2000 --cpu-seconds 5 --e2e-iters 0 ;;
-    benchc4dr) step bench_c4dr 400 python bench.py --config c4dr --steps 1000 --cpu-seconds 5 --e2e-iters 0 ;;
-    benchmix) step bench_c3mix 400 python bench.py --config c3mix --steps 2000 --cpu-seconds 10 --e2e-iters 0 ;;
+    benchmixr) step bench_c3mixr 400 python bench.py --config c3mixr --steps 2000 --full --cpu-seconds 5 --e2e-iters 0 ;;
+    benchc4dr) step bench_c4dr 400 python bench.py --config c4dr --steps 1000 --full --cpu-seconds 5 --e2e-iters 0 ;;
+    benchmix) step bench_c3mix 400 python bench.py --config c3mix --steps 2000 --full --cpu-seconds 10 --e2e-iters 0 ;;
     prof)
       export TMPDIR=/tmp
       step prof_kt 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_kt -o kt --output-format csv -- python bench.py --steps 1000 --no-cpu-baseline --e2e-iters 0
@@ -104,18 +104,22 @@ for s in "$@"; do
       ;;
     profe2e)
       export TMPDIR=/tmp
+      export QS_BENCH_FULL=1   # the end_to_end leg runs only in a full bench (bench.py --full)
       step profe2e_kt 600 rocprofv3 --kernel-trace --stats -d gpurun_out/profe2e_kt -o kt --output-format csv -- python bench.py --config a8 --steps 200 --no-cpu-baseline --e2e-iters 1 --e2e-steps 64
       step profe2e_c3_kt 600 rocprofv3 --kernel-trace --stats -d gpurun_out/profe2e_c3_kt -o kt --output-format csv -- python bench.py --config c3 --steps 200 --no-cpu-baseline --e2e-iters 1
       rm -f gpurun_out/profe2e_kt/*kernel_trace.csv gpurun_out/profe2e_c3_kt/*kernel_trace.csv
       ;;
     tune)
+      export QS_BENCH_FULL=1   # bench.py --full: the end_to_end leg is what gets tuned
       step tune_a8 900 env PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=1 PYTORCH_TUNABLEOP_VERBOSE=1 PYTORCH_TUNABLEOP_FILENAME=gpurun_out/tunableop_a8_%d.csv python bench.py --config a8 --steps 200 --no-cpu-baseline --e2e-iters 1 --e2e-steps 64
       step tuned_a8 600 env PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=0 PYTORCH_TUNABLEOP_FILENAME=gpurun_out/tunableop_a8_%d.csv python bench.py --config a8 --steps 200 --no-cpu-baseline --e2e-iters 1 --e2e-steps 64
       ;;
     tunec3)
+      export QS_BENCH_FULL=1
       step tune_c3 1100 env PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=1 PYTORCH_TUNABLEOP_MAX_TUNING_ITERATIONS=20 PYTORCH_TUNABLEOP_FILENAME=gpurun_out/tunableop_c3_%d.csv python bench.py --config c3 --steps 200 --no-cpu-baseline --e2e-iters 1
       ;;
     tunea512)
+      export QS_BENCH_FULL=1
       step tune_a512 1100 env PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=1 PYTORCH_TUNABLEOP_MAX_TUNING_ITERATIONS=20 PYTORCH_TUNABLEOP_FILENAME=gpurun_out/tunableop_a512_%d.csv python bench.py --config a8 --steps 200 --no-cpu-baseline --e2e-iters 1
       ;;
     profc4)
@@ -153,7 +157,7 @@ for s in "$@"; do
       step profpol2_pmc 200 timeout -s KILL 180 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_WAIT_INST_LDS SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES --kernel-include-regex attn -d gpurun_out/profpol2_pmc -o p --output-format csv -- python tools/rollout_prof.py c3
       ;;
     n128) step gpu_tests_n128 900 python -u -m pytest tests/test_gpu_n128.py -x -v --timeout 300 --timeout-method thread ;;
-    benchn128) step bench_n128 300 python bench.py --config n128 --steps 500 --cpu-seconds 5 --e2e-iters 0 ;;
+    benchn128) step bench_n128 300 python bench.py --config n128 --steps 500 --full --cpu-seconds 5 --e2e-iters 0 ;;
     prioab)    # the younger-wave priority flip (QS_PRIO_AT, default 11) against off, per config
       for c in c3 c4 c3mix c5 c2; do
         CONFIG=$c STEPS=1000 step prioab_$c 300 bash tools/ab_jit.sh on: off:-DQS_PRIO_AT=-1 on2: off2:-DQS_PRIO_AT=-1
@@ -167,7 +171,7 @@ for s in "$@"; do
     final)     # the committed tree: smoke, the whole -m gpu suite, the default bench line
       step smoke_final 400 python -c "import __graft_entry__ as g; g.smoke()"
       step gpu_suite_final 1000 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread
-      step bench_default 900 python bench.py
+      step bench_default 900 python bench.py --full
       ;;
     profall)   # CONFIGS (default "c3 c2 a8 c3mix c4 c5"): profcfg per config
       for c in ${CONFIGS:-c3 c2 a8 c3mix c4 c5}; do
@@ -190,6 +194,7 @@ for s in "$@"; do
     polab)     # policy-kernel A/B: one C3 end-to-end iteration under a kernel trace per library (LIBS="name ...",
                # quadswarm_amd/lib/ab/libquadswarm_<name>.so from tools/build_pol_variant.sh; "base" = the in-tree library)
       export TMPDIR=/tmp
+      export QS_BENCH_FULL=1   # bench.py --full: the end-to-end iteration is what gets traced
       for v in ${LIBS:?LIBS=<variant names>}; do
         if [ "$v" = base ]; then unset QUADSWARM_LIB; else
           export QUADSWARM_LIB=$PWD/quad-swarm-rl-stable-baselines3_amd/quadswarm_amd/lib/ab/libquadswarm_$v.so; fi
@@ -202,17 +207,18 @@ for s in "$@"; do
       ;;
     e2eprof)   # kernel trace of one C3 end-to-end PPO iteration (where update_s goes)
       export TMPDIR=/tmp
+      export QS_BENCH_FULL=1   # bench.py --full: the end_to_end leg
       step e2eprof_kt 500 rocprofv3 --kernel-trace --stats -d gpurun_out/e2eprof -o e2e --output-format csv -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --e2e-iters 1
       python3 tools/kstats.py gpurun_out/e2eprof > gpurun_out/e2eprof_summary.txt 2>&1
       find gpurun_out/e2eprof -name "*kernel_trace.csv" -delete
       ;;
     a8e2e)     # flavor-A end to end (sb_train settings, n_steps 64) with the fused update vs torch fp32
       for up in x3 fp32; do
-        step a8_e2e_$up 500 python bench.py --config a8 --steps 100 --no-cpu-baseline --e2e-iters 1 --e2e-steps 64 --e2e-update-precision $up
+        step a8_e2e_$up 500 python bench.py --config a8 --steps 100 --full --no-cpu-baseline --e2e-iters 1 --e2e-steps 64 --e2e-update-precision $up
       done
       ;;
     torchrun1) # the N > 1 launch path rehearsed at world size 1: RCCL initialised (QS_BENCH_DIST=1)
-      step bench_torchrun1 600 env QS_BENCH_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 2000 --no-cpu-baseline
+      step bench_torchrun1 600 env QS_BENCH_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 2000 --full --no-cpu-baseline
       ;;
     window)    # the driver's 20-step window: its split (tools/window_probe.py) and a per-dispatch trace of the driver command
       export TMPDIR=/tmp
