@@ -60,6 +60,12 @@ struct KP {
     // ---- per-step reward components (qs_config.step_infos): the step writes buffers.rew_info
     int rcomp;
 };
+// KP::scen_b >= 0: the goal scenarios of gym_art/quadrotor_multi/scenarios/ (qs_scen.h)
+enum { SC_STATIC_SAME_GOAL = 0, SC_STATIC_DIFF_GOAL, SC_EP_LISSAJOUS3D, SC_EP_RAND_BEZIER, SC_DYNAMIC_SAME_GOAL,
+       SC_DYNAMIC_DIFF_GOAL, SC_DYNAMIC_FORMATIONS, SC_SWAP_GOALS, SC_SWARM_VS_SWARM, SC_RUN_AWAY, SC_MIX,
+       // the obstacle maps' dynamic scenarios (scenarios/obstacles/, QUADS_MODE_LIST_OBSTACLES_TEST utils.py:18-20):
+       // reset with the env's map by obstacle_reset_env (qs_flavor_b.h), stepped by scen_step_lane
+       SC_O_SWAP_GOALS, SC_O_EP_RAND_BEZIER, SC_O_DYNAMIC_SAME_GOAL };
 
 // The fields qs_set_param may change after creation, read once per launch into registers (uniform):
 // kernels use `kpm.` for them so that neither build re-loads them inside loops.
@@ -120,38 +126,79 @@ struct Bufs {
     float* rcomp;                // [QS_NRI, I] the step's reward components (kp.rcomp)
 };
 
-// The buffer pointers as VGPR values (QS_VPTR): a step kernel's uniform state outgrows the 102 SGPRs, and the
-// compiler then loads the kernel's pointer arguments in small batches, each waited for and spilled to VGPR lanes
-// before the next (five kernarg round trips at the start of the flavor-B mix kernel).  Moving them to VGPRs at
-// entry issues every argument load at once, waits once, and keeps them out of the SGPR budget (2 VGPRs each; the
-// per-lane addresses are VGPR arithmetic anyway).
-#ifndef QS_VPTR
-#define QS_VPTR 0   // measured slower on every flavor-B config (round 5: C3 8.00 vs 7.47 us); kept for A/B
+// ---------------------------------------------------------------------------------------------
+// Launch geometry and the LDS map: the one definition that the kernels (their lane -> env / drone indexing and
+// their LDS pointers) and the host (block size, grid, dynamic LDS bytes of the launch) both read.  Plain constexpr
+// functions of integers: the same code on the host, on the device and under hipRTC.
+// ---------------------------------------------------------------------------------------------
+// Sub-lanes per drone of the step kernels: flavor B (QS_QB), flavor A (QS_QA), and an env that spans several waves
+// (QS_QW: with 2, a 512-env 64-drone shard or a 256-env 128-drone shard is 1024 waves, one per SIMD).  Specialised
+// kernels get QS_QB / QS_QA from the host (qs_specialize).
+#ifndef QS_QB
+#define QS_QB 4
 #endif
-template <class T, bool ON = true>
-__device__ __forceinline__ void vptr(T*& p) {
-#if QS_VPTR
-    if constexpr (!ON) return;
-    uint64_t x = reinterpret_cast<uint64_t>(p);
-    asm volatile("" : "+v"(x));
-    // back through a global (address space 1) pointer: the accesses stay global_* (a plain cast would make them
-    // generic -> flat_*)
-    typedef __attribute__((address_space(1))) T GT;
-    p = (T*)(reinterpret_cast<GT*>(x));
-#else
-    (void)p;
+#ifndef QS_QA
+#define QS_QA 2
 #endif
+#ifndef QS_QW
+#define QS_QW 2
+#endif
+struct Geo {
+    int Q;       // lanes per drone
+    int LPE;     // lanes per env
+    int WGS;     // threads per workgroup: one wave, or the env's waves
+    int EPB;     // envs per workgroup
+    int SLOTS;   // drone slots (LDS rows) per workgroup
+};
+constexpr Geo geo_of(int npad, int q) {
+    const int lpe = npad * q, wgs = lpe > 64 ? lpe : 64, epb = wgs / lpe;
+    return Geo{q, lpe, wgs, epb, epb * npad};
 }
-// ON: the kernels whose VGPR budget has the room (flavor B up to 16 drone slots: 181 -> 226 VGPRs at C3, still two
-// waves per SIMD; the 32-slot kernel would cross 256 and lose its second wave)
-template <bool ON>
-__device__ __forceinline__ void vptr_bufs(Bufs& b) {
-    vptr<float, ON>(b.st); vptr<int32_t, ON>(b.ist); vptr<int32_t, ON>(b.env); vptr<float, ON>(b.envf);
-    vptr<float2, ON>(b.obst); vptr<float, ON>(b.stale); vptr<float, ON>(b.obs); vptr<float, ON>(b.term);
-    vptr<float, ON>(b.rew); vptr<uint8_t, ON>(b.done); vptr<uint8_t, ON>(b.rinfo); vptr<const float, ON>(b.act);
-    vptr<const uint8_t, ON>(b.mask); vptr<unsigned long long, ON>(b.stats); vptr<float, ON>(b.estats);
-    vptr<float, ON>(b.rcomp);
+// Step kernels: q lanes per drone while the env fits a wave, else 64 / npad; the multi-wave envs (flavor B from 64
+// drones, flavor A -- whose 64-drone env stays one wave of single lanes -- from 128) take QS_QW.
+constexpr Geo step_geo(int npad, int q, bool flavor_a) {
+    return geo_of(npad, npad * q <= 64 ? q : ((flavor_a ? npad > 64 : npad >= 64) ? QS_QW : 64 / npad));
 }
+// the explicit reset kernels: one lane per drone
+constexpr Geo reset_geo(int npad) { return geo_of(npad, 1); }
+
+// Dynamic LDS of a launch, as word (4-byte) offsets:
+//   obs    [slots, obs_dim]   the observation tile (free as scratch until the obs phase of a step)
+//   xch    [slots] x 2 float4 the neighbour exchange tile
+//   scr    64 words           env collectives / flags (QS_B_SCR_* / QS_A_SCR_* below)
+//   otile  [epb, M] float2    obstacle kernels: the envs' pillar lists
+//   oscr   [epb]              obstacle kernels: QS_OBST_SCRATCH bytes of reset scratch per env (ObstScratch)
+//   tab    [epb]              kernels with goal tables: scen_stride(npad) words per env
+constexpr int QS_OBST_SCRATCH = 400;
+// goal tables of an env: 2 x (npad + 4) rows of 4 floats, then the env's scenario record (SC_WORDS words, padded
+// to 32; the flavor-B step kernel's copy for scen_step_lane)
+constexpr int scen_stride(int npad) { return 2 * (npad + 4) * 4 + 32; }
+// do the launch's kernels keep goal tables?  A goal scenario (KP::scen_b >= 0); with obstacles, a dynamic one
+constexpr bool scen_tables(bool obst, int scen_b) { return obst ? scen_b >= SC_O_SWAP_GOALS : scen_b >= 0; }
+// The map of a launch of geometry g (g.SLOTS drone rows, g.EPB envs per workgroup); obst: an obstacle kernel with
+// M pillar slots per env.
+struct LdsMap {
+    int obs, xch, scr, otile, oscr, tab;
+};
+constexpr LdsMap lds_map(Geo g, int obs_dim, int M, bool obst) {
+    LdsMap m{};
+    m.obs = 0;
+    m.xch = g.SLOTS * obs_dim;
+    m.scr = m.xch + g.SLOTS * 8;
+    m.otile = m.scr + 64;
+    m.oscr = m.otile + (obst ? g.EPB * 2 * M : 0);
+    m.tab = m.oscr + (obst ? g.EPB * (QS_OBST_SCRATCH / 4) : 0);
+    return m;
+}
+// the launch's total, what the host allocates (tables: scen_tables(); the kernels index by the offsets alone)
+constexpr int lds_words(const LdsMap& m, Geo g, int npad, bool tables) {
+    return m.tab + (tables ? g.EPB * scen_stride(npad) : 0);
+}
+// words of `scr`.  Flavor B's multi-wave envs: the EnvColl ballot slots from word 0, the episode counters' exchange
+// at QS_B_SCR_CNT.  Flavor A: the env-finished flags (one per env of the workgroup) from QS_A_SCR_FIN, then for the
+// multi-wave envs the collectives' scratch (EnvColl ballots, float sums), the episode counters and env drone 0's goal
+constexpr int QS_B_SCR_CNT = 16;
+constexpr int QS_A_SCR_FIN = 0, QS_A_SCR_BITS = 16, QS_A_SCR_SUM = 32, QS_A_SCR_CNT = 48, QS_A_SCR_GOAL0 = 60;
 
 // Diagnostic phase stamps (build with -DQS_STAMPS=1 only; never in the shipped library): lane 0 of
 // each block records s_memtime at phase boundaries; tools/phase_stamps.py reads them back.  A stamp waits
@@ -343,12 +390,6 @@ __device__ __forceinline__ void load_drone(const KP& kp, const Bufs& b, int g, D
 // written back by the end-of-kernel release (MI355X_MICROARCH "boundary": + dirty bytes / 6 TB/s).
 // They are raw buffer stores with the sc1 cache-policy bit (aux 16): compiler-visible builtins, so the
 // hazard recognizer schedules the wait states of the SGPR descriptor like for any other store.
-#ifndef QS_WT_OBS
-#define QS_WT_OBS 1
-#endif
-#ifndef QS_WT_STATE
-#define QS_WT_STATE 1
-#endif
 constexpr int QS_AUX_SC1 = 16;
 typedef uint32_t qs_v4u __attribute__((ext_vector_type(4)));
 // buffer descriptor over a uniform base (raw, stride 0, 32-bit offsets; gfx950 dword3 0x00020000)
@@ -359,14 +400,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t qs_rsrc(const void* base) {
 __device__ __forceinline__ void st_wt4(__amdgpu_buffer_rsrc_t r, uint32_t voff, float4 v) {
     const qs_v4u x = {(uint32_t)__float_as_int(v.x), (uint32_t)__float_as_int(v.y), (uint32_t)__float_as_int(v.z),
                       (uint32_t)__float_as_int(v.w)};
-    __builtin_amdgcn_raw_buffer_store_b128(x, r, (int)voff, 0, QS_WT_OBS ? QS_AUX_SC1 : 0);
+    __builtin_amdgcn_raw_buffer_store_b128(x, r, (int)voff, 0, QS_AUX_SC1);
 }
 // 4-B store of word `v` at (uniform soff + per-lane voff) bytes from the descriptor's base
-#ifndef QS_STATE_AUX   // cache policy of the state stores: sc1 (write-through), or QS_STATE_AUX=2 (nt) / 0 (plain)
-#define QS_STATE_AUX (QS_WT_STATE ? QS_AUX_SC1 : 0)
-#endif
 __device__ __forceinline__ void st_wt1(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, uint32_t v) {
-    __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)voff, (int)soff, QS_STATE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)voff, (int)soff, QS_AUX_SC1);
 }
 // field f of a SoA array at (uniform base, lane byte offset): the field offset rides in soffset
 template <typename T>
@@ -664,15 +702,10 @@ __device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\
 // exchanged through DPP quad permutes (a VALU modifier: no LDS round trip).  Every helper below
 // must be called with all Q lanes of the drone active (quad-uniform control flow).
 // ---------------------------------------------------------------------------------------------
-// QS_DPP_BC: bound_ctrl on (an out-of-range / disabled source lane reads 0 -- the same value as the old = 0
-// form, so bitwise the same results) lets the compiler fold the permute into its consumer (v_sub_f32_dpp ...)
-// more often: C3 7.74 -> 7.64 us (profiles/ab/r03_dpp_bc_ab.txt); flavor A kept it off in round 3 and takes it
-// since round 4 (a8 23.54 -> 23.37 us, profiles/ab/r04_a8_dpp_bc_ab.txt)
-#ifndef QS_DPP_BC
-#define QS_DPP_BC 1
-#endif
+// bound_ctrl on (an out-of-range / disabled source lane reads 0 -- the same value as the old = 0 form) lets the
+// compiler fold the permute into its consumer (v_sub_f32_dpp ...) more often
 template <int CTRL>
-__device__ __forceinline__ int dpp_i(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, QS_DPP_BC != 0); }
+__device__ __forceinline__ int dpp_i(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true); }
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float x) { return __int_as_float(dpp_i<CTRL>(__float_as_int(x))); }
 constexpr int quad_perm(int a, int b, int c, int d) { return a | (b << 2) | (c << 4) | (d << 6); }
@@ -757,12 +790,6 @@ __device__ __forceinline__ void qdraws(const Rng& r, uint32_t id, uint32_t sn, u
 __device__ __forceinline__ int xcd_block(int b, int nblocks) {
     return (nblocks & 7) ? b : (b & 7) * (nblocks >> 3) + (b >> 3);
 }
-
-// Sub-lanes per drone of an env that spans several waves (64- and 128-drone envs): with 2, a 512-env
-// 64-drone shard or a 256-env 128-drone shard is 1024 waves, one per SIMD.
-#ifndef QS_QW
-#define QS_QW 2
-#endif
 
 // ---- collision rows: bit j = partner drone j; 64 bits, or two words for the 128-drone envs ----
 struct Row128 {
@@ -899,13 +926,10 @@ __device__ constexpr int tile_vecs() {
 // instead of one per vector (the loop above waits on each read before its store).  Reads past the tile are
 // clamped to its last vector (stored by its own lane only); the non-finite count is the loop's, taken exactly in
 // the rare branch.  V = tile_vecs<>() bounds the vectors per lane; a larger tile falls back to the loop.
-#ifndef QS_TILE_BATCH
-#define QS_TILE_BATCH 1
-#endif
 template <int V>
 __device__ __forceinline__ int tile_store_v(const float* lds, float* dst, int nfloat, int lane, int nthr) {
     const int nvec = nfloat >> 2;
-    if (!QS_TILE_BATCH || V <= 0 || V > 8 || (((uintptr_t)dst) & 15) != 0 || nvec < 1 || nvec > V * nthr)
+    if (V <= 0 || V > 8 || (((uintptr_t)dst) & 15) != 0 || nvec < 1 || nvec > V * nthr)
         return tile_store(lds, dst, nfloat, lane, nthr);
     const float4* lv = reinterpret_cast<const float4*>(lds);
     const __amdgpu_buffer_rsrc_t r = qs_rsrc(dst);

@@ -54,25 +54,6 @@ __device__ __forceinline__ float sin_small(float x) {
     return x * (1.f + x2 * (-1.f / 6.f + x2 * (1.f / 120.f + x2 * (-1.f / 5040.f + x2 * (1.f / 362880.f + x2 * (-1.f / 39916800.f))))));
 }
 
-#ifndef QS_CAM_RCP
-#define QS_CAM_RCP 1
-#endif
-#ifndef QS_CAM_SECTOR
-#define QS_CAM_SECTOR 1
-#endif
-#ifndef QS_PID_MED3
-#define QS_PID_MED3 1
-#endif
-#ifndef QS_A_DEAL_SENSE
-#define QS_A_DEAL_SENSE 1
-#endif
-#ifndef QS_COL_FOLD
-#define QS_COL_FOLD 1
-#endif
-#ifndef QS_ACT_FOLD
-#define QS_ACT_FOLD 1
-#endif
-
 // (x + pi) % (2 pi) - pi with Python's modulo sign convention.  For r = x + pi in [-2 pi, 4 pi) -- every
 // angle the step wraps -- fmodf(r, 2 pi) is r itself below 2 pi and r - 2 pi above (exact by Sterbenz), so
 // the fast path gives fmodf's bits without its ~30-instruction loop; anything else (and NaN / inf) takes it.
@@ -100,16 +81,12 @@ __device__ __forceinline__ float pid_update(const KP& kp, int k, float e, float*
     st[0] = e;
     float out = kp.pkp[k] * e + kp.pkd[k] * diff + kp.pki[k] * st[1];
     const float sat = kp.psat[k];
-#if QS_PID_MED3
     // the clamp as one v_med3_f32 (the same value for every non-NaN out, -0 and +-inf included); NaN passes through
     // as in the reference's if / elif
     if (sat > 0.f) {
         const float c = __builtin_amdgcn_fmed3f(out, -sat, sat);
         out = out != out ? out : c;
     }
-#else
-    if (sat > 0.f) out = out >= sat ? sat : (out <= -sat ? -sat : out);
-#endif
     const float aw = kp.paw[k];
     if (aw > 0.f && -aw < out && out < aw) st[1] += e * kp.dt;
     return out;
@@ -219,7 +196,6 @@ __device__ __forceinline__ void camera(const KP& kp, float rx, float ry, float g
     float s, c;
     sincos_hw(-ga, &s, &c);
     const float rp0 = c * rx - s * ry, rp1 = s * rx + c * ry;
-#if QS_CAM_SECTOR
     // get_camera_angle (get_state.py:128-137) without the atan2: the camera whose axis k seg is nearest the
     // bearing is the one with the largest projection rp . (cos k seg, sin k seg) (the first on an exact tie; the
     // reference's round() differs only on the sector boundaries, where the features are ill-conditioned anyway).
@@ -238,22 +214,12 @@ __device__ __forceinline__ void camera(const KP& kp, float rx, float ry, float g
     }
     s = -sa;   // sincos(-cam)
     c = ca;
-#else
-    float m = atan2f(rp1, rp0);   // fmodf(m, 2 pi) is m itself: |atan2| <= pi
-    if (m < 0.f) m += k2Pi;
-    const float seg = k2Pi / (float)kp.n_cam;
-    const int ci = ((int)rintf(m / seg)) % kp.n_cam;
-    const float cam = (float)ci * seg;
-    sincos_hw(-cam, &s, &c);
-#endif
     const float c0 = c * rp0 - s * rp1, c1 = s * rp0 + c * rp1;
     const float cn2 = c0 * c0 + c1 * c1, cn = fsqrt(cn2);
     const float r = kp.cam_r, r2 = r * r;
     const float pxs = kp.cam_w / (kp.cam_res * kp.cam_f);  // pixel -> tan(angle)
-#if QS_CAM_RCP
     // the quotients as products with hardware reciprocals (~1 ulp each, like target_step): 1 / |c| once for
-    // a, mf and the perpendicular; the camera index (m / seg above) keeps its IEEE division, since a rounding
-    // flip there would move the segment.  0 / inf / NaN cases as the divisions give them (x * rcp(0) = +-inf,
+    // a, mf and the perpendicular.  0 / inf / NaN cases as the divisions give them (x * rcp(0) = +-inf,
     // 0 * rcp(0) = NaN)
     const float icn = frcp(cn);
     const float a = r2 * icn;
@@ -267,18 +233,6 @@ __device__ __forceinline__ void camera(const KP& kp, float rx, float ry, float g
     const float at1 = atanf(x11 * frcp(x10) + n1 * pxs), at2 = atanf(x21 * frcp(x20) + n2 * pxs);
     const float alpha = fabsf(at1 - at2);
     const float l = r * frcp(sin_small(0.5f * alpha));
-#else
-    const float a = r2 / cn;
-    const float h = sqrtf(r2 - a * a);                   // NaN when the target is inside the marker
-    const float mf = 1.f - r2 / cn2;
-    const float mid0 = c0 * mf, mid1 = c1 * mf;
-    const float pe0 = c1 / cn, pe1 = -c0 / cn;
-    const float x10 = mid0 + h * pe0, x11 = mid1 + h * pe1;
-    const float x20 = mid0 - h * pe0, x21 = mid1 - h * pe1;
-    const float at1 = atanf(x11 / x10 + n1 * pxs), at2 = atanf(x21 / x20 + n2 * pxs);
-    const float alpha = fabsf(at1 - at2);
-    const float l = r / sin_small(0.5f * alpha);
-#endif
     const float ar = wrap_pi(0.5f * (at1 + at2) + cam);
     dist = (l != l) ? 0.f : l;
     ang = (ar != ar) ? 0.f : ar;
@@ -468,9 +422,7 @@ __device__ __forceinline__ void neighbor_obs_a(const KP& kp, const float4* xch, 
 // the k smallest (key, j) in a sorted register list by insertion; the Q lists are merged over DPP, so every
 // sub-lane holds the env's k nearest in the order the rank formula of neighbor_obs_a gives (key, then index).
 // Sub-lane q then writes slots q, q + Q, ... with the obs-pass noise.  k <= QS_A_KMAX (qs_step.hip validate).
-#ifndef QS_A_KMAX
-#define QS_A_KMAX 16
-#endif
+constexpr int QS_A_KMAX = 16;   // (the host's validate and the Python wrapper refuse a larger k)
 template <int NPAD, int Q = 1>
 __device__ __forceinline__ void neighbor_obs_wide(const KP& kp, const float4* xch, int base, int di, const float* P, float H,
                                                   float aw, const float* V, const Rng& rng, uint32_t gid, bool reset,
@@ -704,8 +656,8 @@ __device__ __forceinline__ void col_row16_q2(const KP& kp, const Drone& d, int d
         const int j = dpp_i<C>(di);
         // only the K = 0 rotation can bring the drone itself (its own other sub-lane); with 8 drones every slot of the
         // row is a drone (constants in the specialised kernels: the two tests fold away)
-        const bool self_ok = (QS_COL_FOLD && K != 0) || j != di;
-        const bool in_env = (QS_COL_FOLD && kp.N == 8) || j < kp.N;
+        const bool self_ok = K != 0 || j != di;
+        const bool in_env = kp.N == 8 || j < kp.N;
         const bool hit = self_ok & in_env & (dx * dx + dy * dy + dz * dz <= thr2);   // a select, not a branch
         cur |= hit ? (1u << j) : 0u;   // j < 8: the row's low word
         col_row16_q2<K + 1>(kp, d, di, thr2, cur);
@@ -735,9 +687,6 @@ __device__ __forceinline__ void scen_reset_a(const KP& kp, const Bufs& b, float*
 // chain (controller, physics) is replicated on the sub-lanes; the divisible work is dealt over them:
 // the per-tick OU blocks (sub-lane q draws tick t + q's block, DPP broadcast) and the neighbour
 // features (neighbour j on sub-lane j % Q).  Reductions over the env keep the one-lane-per-drone tree.
-#ifndef QS_QA
-#define QS_QA 2
-#endif
 // tick (t + k)'s OU normals from sub-lane k: k = 0 -> z, k >= 1 -> zn[k - 1]
 template <int Q, int K = 0>
 __device__ __forceinline__ void qbc_ticks(const float (&zr)[4], float (&z)[4], float (&zn)[Q > 1 ? Q - 1 : 1][4]) {
@@ -751,30 +700,9 @@ __device__ __forceinline__ void qbc_ticks(const float (&zr)[4], float (&z)[4], f
         qbc_ticks<Q, K + 1>(zr, z, zn);
     }
 }
+// (128-drone envs: QS_QW sub-lanes, the env is a workgroup of 4 waves -- one per SIMD at 256 envs; qs_common.h step_geo)
 template <int NPAD>
-struct StepGeoA {
-    // 128-drone envs: QS_QW sub-lanes, the env is a workgroup of 4 waves (one per SIMD at 256 envs)
-    static constexpr int Q = NPAD * QS_QA <= 64 ? QS_QA : (NPAD > 64 ? QS_QW : 64 / NPAD);
-    static constexpr int LPE = NPAD * Q;        // lanes per env
-    static constexpr int WGS = LPE > 64 ? LPE : 64;   // threads per workgroup: one wave, or the env's waves
-    static constexpr int EPB = WGS / LPE;       // envs per workgroup
-    static constexpr int SLOTS = EPB * NPAD;    // drone slots (LDS rows) per workgroup
-    static constexpr bool WIDE = LPE > 64;      // the env spans the workgroup's waves
-};
-// the explicit reset kernel: one lane per drone
-template <int NPAD>
-struct ResetGeoA {
-    static constexpr int WGS = NPAD > 64 ? NPAD : 64;
-    static constexpr int EPB = WGS / NPAD;
-    static constexpr int SLOTS = EPB * NPAD;
-};
-// LDS words after the exchange tile (64 words before the scenario tables, qs_scen.h scen_tab): the env-finished
-// flags (one per env of the workgroup), then for the multi-wave envs the collectives' scratch (EnvColl ballots at
-// words 16-31, float sums at 32-47), the episode counters (48-58) and env drone 0's goal (60-62)
-constexpr int QS_A_SCR_BITS = 16, QS_A_SCR_SUM = 32, QS_A_SCR_CNT = 48, QS_A_SCR_GOAL0 = 60;
-
-template <int NPAD>
-__global__ __launch_bounds__(StepGeoA<NPAD>::WGS) void step_kernel_a(const KP* __restrict__ kpp, Bufs b) {
+__global__ __launch_bounds__(step_geo(NPAD, QS_QA, true).WGS) void step_kernel_a(const KP* __restrict__ kpp, Bufs b) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     QS_BIND_KP(kpp);
     const uint32_t seed = kpm.seed;
@@ -785,9 +713,10 @@ __global__ __launch_bounds__(StepGeoA<NPAD>::WGS) void step_kernel_a(const KP* _
     QS_STAMP_ACC_DECL
     QS_RTSTAMP(12);
     QS_STAMP_MARK();
-    using G = StepGeoA<NPAD>;
-    constexpr int Q = G::Q, LPE = G::LPE, EPB = G::EPB, SLOTS = G::SLOTS, WGS = G::WGS;
-    constexpr bool WIDE = G::WIDE;
+    constexpr Geo G = step_geo(NPAD, QS_QA, true);
+    constexpr int Q = G.Q, LPE = G.LPE, EPB = G.EPB, SLOTS = G.SLOTS, WGS = G.WGS;
+    constexpr bool WIDE = LPE > 64;   // the env spans the workgroup's waves
+    auto L = [&] { return lds_map(G, kp.obs_dim, 0, false); };   // the LDS map, evaluated where a pointer is taken
     const int lane = threadIdx.x;
     const int el = lane / LPE, di = (lane % LPE) / Q, q = lane % Q;
     const int env0 = blockIdx.x * EPB;
@@ -800,10 +729,11 @@ __global__ __launch_bounds__(StepGeoA<NPAD>::WGS) void step_kernel_a(const KP* _
     const int sbase = el * NPAD;          // first drone slot of the env
     const int nenv_blk = min(EPB, kp.E - env0);
     const int rows = nenv_blk * kp.N;
-    float* row = lds + (size_t)(el * kp.N + di) * kp.obs_dim;
-    float4* xch = reinterpret_cast<float4*>(lds + SLOTS * kp.obs_dim);
-    int* efin = reinterpret_cast<int*>(lds + SLOTS * kp.obs_dim + SLOTS * 8);
-    EnvA<NPAD, Q> ev(base, reinterpret_cast<uint64_t*>(efin + QS_A_SCR_BITS), reinterpret_cast<float*>(efin + QS_A_SCR_SUM));
+    float* row = lds + L().obs + (size_t)(el * kp.N + di) * kp.obs_dim;
+    float4* xch = reinterpret_cast<float4*>(lds + L().xch);
+    int* scr = reinterpret_cast<int*>(lds + L().scr);
+    int* efin = scr + QS_A_SCR_FIN;
+    EnvA<NPAD, Q> ev(base, reinterpret_cast<uint64_t*>(scr + QS_A_SCR_BITS), reinterpret_cast<float*>(scr + QS_A_SCR_SUM));
     using Row = typename RowOf<(NPAD > 64)>::T;
 
     Drone d;
@@ -819,7 +749,7 @@ __global__ __launch_bounds__(StepGeoA<NPAD>::WGS) void step_kernel_a(const KP* _
     const float capr = b.envf[QS_ENVF_CAPTURE * kp.E + eidx];
     const bool repulsive = kp.scenario == QS_SCEN_DYNAMIC_REPULSIVE;
     const bool SCEN = kp.scen_b >= 0;   // a goal scenario of create_scenario: its state lives in the lead lane
-    float* stab = scen_tab(lds, kp, SLOTS) + el * scen_stride<NPAD>();
+    float* stab = lds + L().tab + el * scen_stride(NPAD);
     Scen sc;
     if (SCEN && active && di == 0 && q == 0) scen_load(kp, b, env, sc);
 
@@ -844,7 +774,7 @@ __global__ __launch_bounds__(StepGeoA<NPAD>::WGS) void step_kernel_a(const KP* _
     // Inside the tick loop `active` only masks the env-level collectives (each reads its own env's lanes) and the
     // env's LDS rows -- no global access: an env past E (a partial last block) computes values it never stores, so
     // the loop needs only the drone test, and none when the env's drones fill its lanes (a constant when specialised)
-    const bool active_tick = QS_ACT_FOLD ? (kp.N == NPAD || di < kp.N) : active;
+    const bool active_tick = kp.N == NPAD || di < kp.N;
 #pragma unroll 1   // 8 controller ticks: one copy of the body (I-cache), also when kp.ticks is a constant
     for (int sub = 0; sub < kp.ticks; ++sub) {
         const bool active = active_tick;
@@ -938,7 +868,7 @@ __global__ __launch_bounds__(StepGeoA<NPAD>::WGS) void step_kernel_a(const KP* _
         float g0x = tx, g0y = ty;
         if (!repulsive) {
             if constexpr (WIDE) {   // env drone 0's goal through LDS (read before the next collective's barrier)
-                float* g0 = reinterpret_cast<float*>(efin + QS_A_SCR_GOAL0);
+                float* g0 = reinterpret_cast<float*>(scr + QS_A_SCR_GOAL0);
                 if (threadIdx.x == 0) {
                     g0[0] = d.goal[0];
                     g0[1] = d.goal[1];
@@ -977,7 +907,7 @@ __global__ __launch_bounds__(StepGeoA<NPAD>::WGS) void step_kernel_a(const KP* _
                 for (int k = 0; k < 3; ++k) stab[4 * di + k] = d.goal[k];
             lds_sync();
             // envok: `sc` is loaded only for envs < E (scen_load above); an env past E in a partial last block
-            // runs the tick loop (QS_ACT_FOLD) but must not step a scenario from uninitialised registers
+            // runs the tick loop (active_tick) but must not step a scenario from uninitialised registers
             if (active && envok && di == 0 && q == 0) {
                 SDraw sd = sdraw(rng, gid, S_SCN);
                 scen_step(kp, sc, tick, sd, stab, stab + 4 * (NPAD + 4));
@@ -1008,14 +938,11 @@ __global__ __launch_bounds__(StepGeoA<NPAD>::WGS) void step_kernel_a(const KP* _
     if (lane < EPB) efin[lane] = 0;
     lds_sync();
     if (fin && di == 0 && q == 0) efin[el] = 1;
-#if QS_A_DEAL_SENSE
     if constexpr (Q == 2) {   // the sensor noise's two Philox blocks, one per sub-lane (bitwise the lead's draws)
         float zs[8];
         if (kp.sense) qdraws<Q, 2, 0>(rng_last, gid, S_SENSOR, 0, q, zs, nullptr);
         if (lead) self_obs_a(kp, d, c, gox, goy, rng_last, gid, S_SENSOR, S_SELF_CAM, row, zs);
-    } else
-#endif
-    if (lead) self_obs_a(kp, d, c, gox, goy, rng_last, gid, S_SENSOR, S_SELF_CAM, row);
+    } else if (lead) self_obs_a(kp, d, c, gox, goy, rng_last, gid, S_SENSOR, S_SELF_CAM, row);
     if (kp.K > 0) {
         if constexpr (WIDE)
             neighbor_obs_wide<NPAD, Q>(kp, xch, sbase, di, d.pos, c.angle, c.angle, d.vel, rng_last, gid, false, active, row, q);
@@ -1036,7 +963,7 @@ __global__ __launch_bounds__(StepGeoA<NPAD>::WGS) void step_kernel_a(const KP* _
         if (kp.stats) {   // the finished episodes' episode_extra_stats rows (:886-969)
             float cv[NCNT];
             if constexpr (WIDE) {   // the counters live on lanes 0..10 of wave 0: through LDS
-                int* cs = efin + QS_A_SCR_CNT;
+                int* cs = scr + QS_A_SCR_CNT;
                 if (li < NCNT) cs[li] = cnt[0];
                 lds_sync();
 #pragma unroll
@@ -1124,12 +1051,13 @@ __global__ __launch_bounds__(StepGeoA<NPAD>::WGS) void step_kernel_a(const KP* _
 
 // explicit reset of masked envs (quadrotor_multi_rewards.QuadrotorEnvMulti.reset)
 template <int NPAD>
-__global__ __launch_bounds__(ResetGeoA<NPAD>::WGS) void reset_kernel_a(const KP* __restrict__ kpp, Bufs b) {
+__global__ __launch_bounds__(reset_geo(NPAD).WGS) void reset_kernel_a(const KP* __restrict__ kpp, Bufs b) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     QS_BIND_KP(kpp);
     const uint32_t seed = kpm.seed;
-    using G = ResetGeoA<NPAD>;
-    constexpr int EPB = G::EPB, SLOTS = G::SLOTS, WGS = G::WGS;
+    constexpr Geo G = reset_geo(NPAD);   // one lane per drone
+    constexpr int EPB = G.EPB, SLOTS = G.SLOTS, WGS = G.WGS;
+    auto L = [&] { return lds_map(G, kp.obs_dim, 0, false); };   // the LDS map, evaluated where a pointer is taken
     const int lane = threadIdx.x;
     const int el = lane / NPAD, di = lane % NPAD;
     const int env0 = blockIdx.x * EPB;
@@ -1144,8 +1072,8 @@ __global__ __launch_bounds__(ResetGeoA<NPAD>::WGS) void reset_kernel_a(const KP*
     const int episode = b.env[QS_E_EPISODE * kp.E + eidx];
     const int eflags = b.env[QS_E_FLAGS * kp.E + eidx];
     const Rng rng = env_rng(seed, b.env[QS_E_TICK * kp.E + eidx], episode);
-    float* row = lds + (size_t)(el * kp.N + di) * kp.obs_dim;
-    int* escr = reinterpret_cast<int*>(lds + SLOTS * kp.obs_dim + SLOTS * 8);
+    float* row = lds + L().obs + (size_t)(el * kp.N + di) * kp.obs_dim;
+    int* escr = reinterpret_cast<int*>(lds + L().scr);
     EnvA<NPAD, 1> ev(base, reinterpret_cast<uint64_t*>(escr + QS_A_SCR_BITS), reinterpret_cast<float*>(escr + QS_A_SCR_SUM));
     Drone d;
     load_drone<(NPAD > 64)>(kp, b, g, d);
@@ -1159,12 +1087,12 @@ __global__ __launch_bounds__(ResetGeoA<NPAD>::WGS) void reset_kernel_a(const KP*
     for (int q = 0; q < 3; ++q) sv[q] = stale_valid ? b.stale[q * kp.I + g] : d.vel[q];
     const bool success = eflags & QS_EF_SUCCESS;
     if (kp.scen_b >= 0)
-        scen_reset_a<NPAD>(kp, b, scen_tab(lds, kp, SLOTS) + el * scen_stride<NPAD>(), env, di, sel && di == 0, sel, rng,
+        scen_reset_a<NPAD>(kp, b, lds + L().tab + el * scen_stride(NPAD), env, di, sel && di == 0, sel, rng,
                            kp.id0 + (uint32_t)(env * kp.N), d);
     reset_env_a(kp, d, c, tx, ty, eflags & QS_EF_HAS_POS, inr, sel, rng, gid, kp.id0 + (uint32_t)(env * kp.N), ev);
     if (sel) self_obs_a(kp, d, c, d.goal[0], d.goal[1], rng, gid, S_RESET_SENSOR, S_RESET_SELF_CAM, row);
     if (kp.K > 0) {
-        float4* xch = reinterpret_cast<float4*>(lds + SLOTS * kp.obs_dim);
+        float4* xch = reinterpret_cast<float4*>(lds + L().xch);
         xch_put_a(xch, lane, d.pos, sh, sv);
         lds_sync();
         if constexpr (NPAD > 64)

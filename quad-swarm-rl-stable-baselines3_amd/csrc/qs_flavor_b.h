@@ -5,16 +5,6 @@
 #include "qs_scen.h"
 #include "qs_replay.h"
 
-#ifndef QS_SCW_LATE
-#define QS_SCW_LATE 0   // A/B: the scenario record's loads after the drone state's (default: before)
-#endif
-#ifndef QS_SCW_SKIP
-#define QS_SCW_SKIP 0   // diagnostic only (wrong results): no scenario-record loads, every env reads as static
-#endif
-#ifndef QS_PAIR_ROUNDS
-#define QS_PAIR_ROUNDS 1   // drone-pair impulses in rounds of disjoint pairs (else one pair per iteration)
-#endif
-
 namespace qs {
 
 // ---------------------------------------------------------------------------------------------
@@ -404,8 +394,7 @@ __device__ __forceinline__ void choose_k(const Rng& r, uint32_t id, uint32_t st,
     }
 }
 
-// per-env reset scratch in LDS (QS_OBST_SCRATCH bytes per env)
-constexpr int QS_OBST_SCRATCH = 400;
+// per-env reset scratch in LDS (QS_OBST_SCRATCH bytes per env: qs_common.h lds_map)
 struct ObstScratch {
     uint8_t perm[64], map[64], fr[64], dp[64], sp[32], gl[32], ids[64];
     float ez;
@@ -647,19 +636,6 @@ __device__ __forceinline__ void collide_obstacle(const KP& kp, const OGeo& og, D
     for (int c = 0; c < 3; ++c) d.om[c] += w[c] * iw * mg;
 }
 
-// LDS of a launch with `slots` drone rows per workgroup: obs tile [slots, obs_dim] | exchange tile
-// [slots x 2 float4] | 64 words | obstacle tiles [EPB, M] float2 | obstacle reset scratch [EPB]
-// (qs_lds_bytes() in qs_step.hip sizes it)
-__device__ __forceinline__ float2* obst_tile(float* lds, const KP& kp, int slots) {
-    return reinterpret_cast<float2*>(lds + slots * kp.obs_dim + slots * 8 + 64);
-}
-// the goal-scenario tables (qs_scen.h scen_tab): after the obstacle tiles and reset scratch in obstacle kernels
-template <bool OBST>
-__device__ __forceinline__ float* scen_tab_b(float* lds, const KP& kp, int slots, int epb) {
-    return scen_tab(lds, kp, slots) + (OBST ? epb * (2 * kp.M + QS_OBST_SCRATCH / 4) : 0);
-}
-
-// Geometry of the flavor-B step kernel: Q lanes per drone (Q * NPAD <= 64), EPB envs per wave.
 // Cooperative state load / store of the Q sub-lanes of a drone (flavor-B step).  The drone's state words
 // (33 fp32 fields QS_F_POS .. QS_F_GOAL, then the NIW int fields QS_I_* a swarm of its size uses: 2 for
 // single drones, 3 up to 32, 4 up to 64, 6 at 128 -- StepGeo::NIW) are dealt over the sub-lanes:
@@ -715,9 +691,8 @@ __device__ __forceinline__ void load_words_q(const KP& kp, const Bufs& b, int g,
     }
 }
 // the drone on every sub-lane; stw (if given) gets the STAT_WORDS words as floats
-// DEAL (Q = 4, QS_DEAL_MOTORS): the motor words 18..29 are the sub-lane's own motor's (no broadcast; see motors_dealt4)
-template <int Q, int NW, int NIW = 4, bool DEAL = false>
-__device__ __forceinline__ void unpack_words_q(const DroneWords<Q, NW>& dw, Drone& d, float* stw = nullptr, int q = 0) {
+template <int Q, int NW, int NIW = 4>
+__device__ __forceinline__ void unpack_words_q(const DroneWords<Q, NW>& dw, Drone& d, float* stw = nullptr) {
     constexpr int T = DroneWords<Q, NW>::T, DW = WordsOf<NIW>::DW;
     const uint32_t (&r)[T] = dw.r;
     uint32_t wv[T * Q > DW ? T * Q : DW];
@@ -735,23 +710,11 @@ __device__ __forceinline__ void unpack_words_q(const DroneWords<Q, NW>& dw, Dron
     }
 #pragma unroll
     for (int i = 0; i < 9; ++i) d.rot[i] = __int_as_float((int)wv[QS_F_ROT + i]);
-    if constexpr (DEAL) {
-        static_assert(Q == 4, "dealt motors: one motor per sub-lane");
-        // the sub-lane's word of field F: F + ((q - F) & 3), in register slot (that word) / 4 -- F / 4 or F / 4 + 1
-        auto own = [&](int F) {
-            const int t = (F + ((q - F) & 3)) >> 2;
-            return __int_as_float((int)(t == F / 4 ? r[F / 4] : r[F / 4 + 1]));
-        };
-        const float rd = own(QS_F_ROT_DAMP), cd = own(QS_F_CMD_DAMP), ou = own(QS_F_OU);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { d.rd[i] = rd; d.cd[i] = cd; d.ou[i] = ou; }
-    } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         d.rd[i] = __int_as_float((int)wv[QS_F_ROT_DAMP + i]);
         d.cd[i] = __int_as_float((int)wv[QS_F_CMD_DAMP + i]);
         d.ou[i] = __int_as_float((int)wv[QS_F_OU + i]);
-    }
     }
     constexpr int IW = QS_F_GOAL + 3;
     d.svd = (int32_t)wv[IW + QS_I_SVD];
@@ -816,81 +779,11 @@ __device__ __forceinline__ void store_drone_q(const KP& kp, const Bufs& b, int g
     }
 }
 
-// Dealt motors (QS_DEAL_MOTORS, Q = 4): sub-lane q runs motor m = (q + 2) & 3 of its drone -- the motor whose
-// rot_damp / cmd_damp / OU words (fields 18 + m, 22 + m, 26 + m: word w sits on sub-lane w % 4) that sub-lane already
-// loads and stores, so they need no broadcast.  The drone's Drone::rd / cd / ou hold that motor's value in all four
-// entries on the sub-lane (unpack_words_q<.., DEAL>, reset and the floor branch write every entry; the store takes word
-// F + m from sub-lane q, i.e. the owner's copy).  The motor filter, its noise and its thrust run once per motor
-// instead of four times per lane; thrust and the three torques are summed over the quad by qsum (DPP butterfly: every
-// sub-lane gets the same bits, so the replicated rest of the substep stays bit-identical on the quad).  The sums are
-// (m0 + m1) + (m2 + m3) instead of a running sum over the motors: fp32 reassociation, inside the parity tolerances
-// (the oracle is float64).  Measured slower on C3 / C2 / C4 (7.20 -> 7.28, 5.04 -> 5.08, 9.72 -> 9.82 us,
-// profiles/ab/r06_deal_motors_ab.txt; parity green either way): the quad sums lengthen the wave's dependency chain
-// more than the replicated motor arithmetic costs in issue slots.  Off by default; -DQS_DEAL_MOTORS=1 for A/Bs.
-#ifndef QS_DEAL_MOTORS
-#define QS_DEAL_MOTORS 0
-#endif
-struct MotorK {   // the sub-lane's motor: thrust_max, the three torque-arm coefficients, torque_max * ccw
-    float tmax, p0, p1, p2, tq;
-};
-__device__ __forceinline__ float sel4(int m, float a, float b, float c, float d) {
-    return m == 0 ? a : (m == 1 ? b : (m == 2 ? c : d));
-}
-__device__ __forceinline__ MotorK motor_k(const KP& kp, int m) {
-    MotorK k;
-    k.tmax = sel4(m, kp.thrust_max[0], kp.thrust_max[1], kp.thrust_max[2], kp.thrust_max[3]);
-    k.p0 = sel4(m, kp.pc0[0], kp.pc0[1], kp.pc0[2], kp.pc0[3]);
-    k.p1 = sel4(m, kp.pc1[0], kp.pc1[1], kp.pc1[2], kp.pc1[3]);
-    k.p2 = sel4(m, kp.pc2[0], kp.pc2[1], kp.pc2[2], kp.pc2[3]);
-    k.tq = sel4(m, kp.torque_max[0] * kp.ccw[0], kp.torque_max[1] * kp.ccw[1], kp.torque_max[2] * kp.ccw[2],
-                kp.torque_max[3] * kp.ccw[3]);
-    return k;
-}
-// motors() for the sub-lane's motor (quadrotor_dynamics.py:511-533), the sums over the quad
-__device__ __forceinline__ Torque motors_dealt4(const KP& kp, Drone& d, float cmd, float noise, const MotorK& mk) {
-    float tau = cmd < d.cd[0] ? kp.tau_down : kp.tau_up;
-    tau = fminf(tau, 1.0f);
-    const float r = tau * (fsqrt(cmd) - d.rd[0]) + d.rd[0];
-    const float c = clampf(r * r + cmd * noise, 0.f, 1.f);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { d.rd[k] = r; d.cd[k] = c; }
-    const float th = mk.tmax * (kp.lin == 1.f ? c : (1.f - kp.lin) * c * c + kp.lin * c);
-    Torque t;
-    t.t0 = qsum<4>(mk.p0 * th);
-    t.t1 = qsum<4>(mk.p1 * th);
-    t.t2 = qsum<4>(mk.p2 * th + mk.tq * c);
-    t.sum = qsum<4>(th);
-    return t;
-}
-__device__ __forceinline__ void substep_dealt4(const KP& kp, Drone& d, float cmd, float noise, const MotorK& mk,
-                                               const Rng& rng, uint32_t gid, int s) {
-    const Torque tq = motors_dealt4(kp, d, cmd, noise, mk);
-    {
-        const RodCoef rc = rod_coef(kp, d.rot, d.om);
-        float Rn[9];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            float dr[3];
-            rod_row(rc, i, dr);
-            rod_apply_row(dr, d.rot, Rn + 3 * i);
-        }
-#pragma unroll
-        for (int i = 0; i < 9; ++i) d.rot[i] = Rn[i];
-    }
-    substep_tail(kp, d, tq, rng, gid, s);
-}
-
-// Sub-lanes per drone of the flavor-B step kernel (QS_QB; 64 / NPAD when an env would not fit a wave).
-#ifndef QS_QB
-#define QS_QB 4
-#endif
+// The flavor-B step kernel's launch geometry (qs_common.h step_geo) and what follows from the env's size
 template <int NPAD>
 struct StepGeo {
-    static constexpr int Q = NPAD * QS_QB <= 64 ? QS_QB : (NPAD >= 64 ? QS_QW : 64 / NPAD);
-    static constexpr int LPE = NPAD * Q;            // lanes per env
-    static constexpr int WGS = LPE > 64 ? LPE : 64; // threads per workgroup: one wave, or the env's waves
-    static constexpr int EPB = WGS / LPE;           // envs per workgroup
-    static constexpr int SLOTS = EPB * NPAD;        // drone slots per workgroup
+    static constexpr Geo geo() { return step_geo(NPAD, QS_QB, false); }
+    static constexpr int Q = geo().Q, LPE = geo().LPE, WGS = geo().WGS, EPB = geo().EPB, SLOTS = geo().SLOTS;
     static constexpr bool WIDE = LPE > 64;          // the env spans the workgroup's waves (64 / 128 drones)
     static constexpr bool ROW2 = NPAD > 64;         // 128-bit collision rows (128-drone envs)
     // istate words a step moves per drone (WordsOf): SVD counter, flags, then the previous-collision row's
@@ -962,7 +855,6 @@ template <int NPAD, bool OBST>
 __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __restrict__ kpp, Bufs b, const RArgs* __restrict__ rargs) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     QS_BIND_KP(kpp);
-    vptr_bufs<(NPAD <= 16)>(b);
     const uint32_t seed = kpm.seed;
     QS_STAMP_DECL
     QS_RTSTAMP(12);
@@ -984,14 +876,15 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
     const int dbase = el * NPAD;          // first drone slot of the env
     const int nenv_blk = min(EPB, kp.E - env0);
     const int rows = nenv_blk * kp.N;
-    float* row = lds + (size_t)(el * kp.N + di) * kp.obs_dim;
-    float4* xch = reinterpret_cast<float4*>(lds + SLOTS * kp.obs_dim);
+    auto L = [&] { return lds_map(G::geo(), kp.obs_dim, kp.M, OBST); };   // the LDS map, evaluated where a pointer is taken
+    float* row = lds + L().obs + (size_t)(el * kp.N + di) * kp.obs_dim;
+    float4* xch = reinterpret_cast<float4*>(lds + L().xch);
     const uint64_t lmask = (LPE >= 64) ? ~0ull : ((1ull << LPE) - 1ull);
-    // env-level collectives; WIDE: their LDS slots and the env counters' exchange in the 64 words after xch
-    uint64_t* wscr = reinterpret_cast<uint64_t*>(lds + SLOTS * kp.obs_dim + SLOTS * 8);
+    // env-level collectives; WIDE: their LDS slots and the env counters' exchange in the scratch words
+    uint64_t* wscr = reinterpret_cast<uint64_t*>(lds + L().scr);
     EnvColl<WIDE, G::ROW2, Q, WGS / 64> ec{lbase, lmask, wscr, 0};
-    float2* otile = obst_tile(lds, kp, SLOTS);
-    ObstScratch* oscr = reinterpret_cast<ObstScratch*>(otile + EPB * kp.M);
+    float2* otile = reinterpret_cast<float2*>(lds + L().otile);
+    ObstScratch* oscr = reinterpret_cast<ObstScratch*>(lds + L().oscr);
     const float2* myob = otile + el * kp.M;
     if (OBST)   // the block's obstacle lists -> LDS (ordered by the first lds_sync below)
         for (int k = lane; k < nenv_blk * kp.M; k += WGS) otile[k] = b.obst[(size_t)env0 * kp.M + k];
@@ -1037,19 +930,13 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
 #pragma unroll
         for (int t = 0; t < SRW; ++t) {
             const int w = li + LPE * t;
-            scw[t] = (SCEN_STEP && !QS_SCW_SKIP && envok && w < SC_WORDS) ? scen_word(kp, b, env, w) : 0u;
+            scw[t] = (SCEN_STEP && envok && w < SC_WORDS) ? scen_word(kp, b, env, w) : 0u;
         }
     };
-#if !QS_SCW_LATE
-    load_scw();
-#endif
+    load_scw();   // before the drone's state words (after them measured no faster)
     Drone d;   // every sub-lane holds the whole drone
     DroneWords<Q, LW> dw;
     load_words_q<Q, LW, NIW>(kp, b, g, q, dw, kp.stats ? LW : DW);
-#if QS_SCW_LATE
-    // after the state words: the unpack's wait (in-order vmcnt) then does not include the record's 27 rows
-    load_scw();
-#endif
     __builtin_amdgcn_sched_barrier(0);
     const Rng rng = env_rng(seed, tick0, episode);
     // The step's regular draws: Philox block k of {OU 0, sensor 0, sensor 1, sensor 2} on sub-lane
@@ -1078,8 +965,7 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
     QS_PRIO(11);
     __builtin_amdgcn_sched_barrier(0);
     float stw[STAT_WORDS];
-    constexpr bool DEALM = QS_DEAL_MOTORS && Q == 4;
-    unpack_words_q<Q, LW, NIW, DEALM>(dw, d, stw, q);
+    unpack_words_q<Q, LW, NIW>(dw, d, stw);
     float a[4] = {av.x, av.y, av.z, av.w};
     const int tick = tick0 + 1;
     const bool done = tick > kpm.ep_len;
@@ -1109,23 +995,12 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
     bool floor_now = false;   // drone 0's on the env's flags: its rew_crash feeds the replay wrapper
     float rc_dist, rc_effort, rc_orient, rc_spin;   // compute_reward_weighted's raw terms (per-step infos)
     {
-        if constexpr (DEALM) {   // the sub-lane's motor m (motors_dealt4)
-            const int m = (q + 2) & 3;
-            const float zm = sel4(m, zou[0], zou[1], zou[2], zou[3]), am = sel4(m, a[0], a[1], a[2], a[3]);
-            const float ou = d.ou[0] + (kp.ou_theta * (kp.ou_mu - d.ou[0]) + kp.ou_sigma * zm);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) d.ou[k] = ou;
-            const float cmd = 0.5f * (clampf(am, -1.f, 1.f) + 1.f);
-            const MotorK mk = motor_k(kp, m);
-            for (int s = 0; s < kp.sim_steps; ++s) substep_dealt4(kp, d, cmd, ou, mk, rng, gid, s);
-        } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) d.ou[k] = d.ou[k] + (kp.ou_theta * (kp.ou_mu - d.ou[k]) + kp.ou_sigma * zou[k]);
         float cmds[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) cmds[k] = 0.5f * (clampf(a[k], -1.f, 1.f) + 1.f);
         for (int s = 0; s < kp.sim_steps; ++s) substep(kp, d, cmds, d.ou, rng, gid, s);
-        }
         // compute_reward_weighted (quadrotor_single.py:34-66)
         const float gx = d.goal[0] - d.pos[0], gy = d.goal[1] - d.pos[1], gz = d.goal[2] - d.pos[2];
         const bool on_floor = d.flags & QS_FL_ON_FLOOR;
@@ -1289,7 +1164,6 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
             impulses_wide<NPAD>(kp, rng, lds, ec, d, active ? row_above(newpairs, di) : Row{}, env, di, q, lane, vchanged);
         } else {
         uint64_t pend = active ? row_above(newpairs, di) : 0ull;
-#if QS_PAIR_ROUNDS
         // Rounds of disjoint pairs (round 5).  The reference applies the new pairs one by one in (i, j) order
         // (quadrotor_multi.py:671-676); a pair only reads and writes its two drones, so what matters is that every
         // pair sees its drones after all their earlier pairs.  A round takes every pending pair that is the earliest
@@ -1371,8 +1245,7 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
                 if (go && own) pend &= ~(1ull << jf);
             }
         }
-#endif
-        for (;;) {
+        for (;;) {   // one pair per iteration: what the rounds left (all of it when they did not run)
             const uint64_t bal = __ballot(pend != 0ull && q == 0);
             if (bal == 0ull) break;
             const uint64_t eb = (bal >> lbase) & lmask;
@@ -1460,7 +1333,7 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
     // every lane, the drone's own goal row); envs whose scenario does nothing at this tick skip it, and the
     // scenario record is stored only where it changed.
     float obs_goal[3] = {d.goal[0], d.goal[1], d.goal[2]};
-    float* stab = scen_tab_b<OBST>(lds, kp, SLOTS, EPB) + el * scen_stride<NPAD>();
+    float* stab = lds + L().tab + el * scen_stride(NPAD);
     QS_STAMP(18);   // sub-phases of "impulses+scenario+state store" (slots 18-21)
     if (SCEN_STEP) {
         uint32_t* srec = reinterpret_cast<uint32_t*>(stab + 2 * (NPAD + 4) * 4);
@@ -1573,8 +1446,8 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
         if (kp.stats) {   // the finished episode's episode_extra_stats rows (quadrotor_multi.py:739-831)
             // the env's counters from the lanes that hold them (every lane takes part in the permutes)
             float cv[NCNT];
-            if constexpr (WIDE) {   // counter k lives on lane k (the first wave): through LDS words 16.. of wscr
-                int* cx = reinterpret_cast<int*>(wscr + 8);
+            if constexpr (WIDE) {   // counter k lives on lane k (the first wave): through the scratch words
+                int* cx = reinterpret_cast<int*>(wscr) + QS_B_SCR_CNT;
                 if (li < NCNT) cx[li] = cnt[0];
                 lds_sync();
 #pragma unroll
@@ -1731,12 +1604,14 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
 
 // explicit reset of masked envs (QuadrotorEnvMulti.reset quadrotor_multi.py:440-517)
 template <int NPAD, bool OBST>
-__global__ __launch_bounds__(NPAD > 64 ? NPAD : 64) void reset_kernel(const KP* __restrict__ kpp, Bufs b) {
+__global__ __launch_bounds__(reset_geo(NPAD).WGS) void reset_kernel(const KP* __restrict__ kpp, Bufs b) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     QS_BIND_KP(kpp);
     const uint32_t seed = kpm.seed;
-    constexpr int WGS = NPAD > 64 ? NPAD : 64, EPB = WGS / NPAD, SLOTS = EPB * NPAD;   // one lane per drone
+    constexpr Geo G = reset_geo(NPAD);   // one lane per drone
+    constexpr int WGS = G.WGS, EPB = G.EPB, SLOTS = G.SLOTS;
     constexpr bool WIDE = NPAD > 64;
+    auto L = [&] { return lds_map(G, kp.obs_dim, kp.M, OBST); };   // the LDS map, evaluated where a pointer is taken
     const int lane = threadIdx.x;
     const int el = lane / NPAD, di = lane % NPAD;
     const int env0 = blockIdx.x * EPB;
@@ -1748,7 +1623,7 @@ __global__ __launch_bounds__(NPAD > 64 ? NPAD : 64) void reset_kernel(const KP* 
     const int eidx = inr ? env : 0;
     const int episode = b.env[QS_E_EPISODE * kp.E + eidx];
     const Rng rng = env_rng(seed, b.env[QS_E_TICK * kp.E + eidx], episode);
-    float* row = lds + (size_t)(el * kp.N + di) * kp.obs_dim;
+    float* row = lds + L().obs + (size_t)(el * kp.N + di) * kp.obs_dim;
     Drone d;
     load_drone<WIDE>(kp, b, g, d);
     // stale QuadrotorEnvMulti.vel: the state's vel unless a reset already happened since the last step
@@ -1756,9 +1631,9 @@ __global__ __launch_bounds__(NPAD > 64 ? NPAD : 64) void reset_kernel(const KP* 
     float sv[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) sv[c] = stale_valid ? b.stale[c * kp.I + g] : d.vel[c];
-    float2* otile = obst_tile(lds, kp, SLOTS);
-    ObstScratch* oscr = reinterpret_cast<ObstScratch*>(otile + EPB * kp.M);
-    float* stab = scen_tab_b<OBST>(lds, kp, SLOTS, EPB) + el * scen_stride<NPAD>();
+    float2* otile = reinterpret_cast<float2*>(lds + L().otile);
+    ObstScratch* oscr = reinterpret_cast<ObstScratch*>(lds + L().oscr);
+    float* stab = lds + L().tab + el * scen_stride(NPAD);
     const bool OSCEN = OBST && kp.scen_b >= SC_O_SWAP_GOALS;
     if (OBST) {
         if (sel && di == 0) {
@@ -1795,7 +1670,7 @@ __global__ __launch_bounds__(NPAD > 64 ? NPAD : 64) void reset_kernel(const KP* 
         self_obs(kp, d, rng, kp.id0 + (uint32_t)g, S_RESET_SENSOR, row);
     }
     if (kp.neighbor == QS_NEIGHBOR_POS_VEL && kp.K > 0) {
-        float4* xch = reinterpret_cast<float4*>(lds + SLOTS * kp.obs_dim);
+        float4* xch = reinterpret_cast<float4*>(lds + L().xch);
         xch_put(xch, lane, d.pos, sv);
         lds_sync();
         neighbor_obs<NPAD, 1>(kp, xch, base, di, 0, d.pos, sv, sel, row);

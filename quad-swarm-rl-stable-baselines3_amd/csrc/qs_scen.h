@@ -20,12 +20,8 @@ __device__ __forceinline__ int ufloor(uint32_t w, int m) {
 // dynamic_formations) on goal tables in LDS (4 floats per drone); the drones then read their goal.
 // Mirrors oracle/quadswarm_oracle_scen.c draw for draw: Philox key = the env's drone 0, stream S_SCN
 // (step) / S_SCN_RESET (reset), one 32-bit word per draw in call order.
+// (the scenario ids SC_*, the values of KP::scen_b: qs_common.h)
 // ---------------------------------------------------------------------------------------------
-enum { SC_STATIC_SAME_GOAL = 0, SC_STATIC_DIFF_GOAL, SC_EP_LISSAJOUS3D, SC_EP_RAND_BEZIER, SC_DYNAMIC_SAME_GOAL,
-       SC_DYNAMIC_DIFF_GOAL, SC_DYNAMIC_FORMATIONS, SC_SWAP_GOALS, SC_SWARM_VS_SWARM, SC_RUN_AWAY, SC_MIX,
-       // the obstacle maps' dynamic scenarios (scenarios/obstacles/, QUADS_MODE_LIST_OBSTACLES_TEST utils.py:18-20):
-       // reset with the env's map by obstacle_reset_env (qs_flavor_b.h), stepped by scen_step_lane
-       SC_O_SWAP_GOALS, SC_O_EP_RAND_BEZIER, SC_O_DYNAMIC_SAME_GOAL };
 enum { F_CIRCLE_H = 0, F_CIRCLE_XZ, F_CIRCLE_YZ, F_SPHERE, F_GRID_H, F_GRID_XZ, F_GRID_YZ, F_CUBE };
 
 struct Scen {
@@ -813,12 +809,6 @@ __device__ __forceinline__ void scen_store_size(const KP& kp, const Bufs& b, int
     *scf(b.envf, kp.E, env, QS_ENVF_SC_SPEED) = s.speed;
 }
 
-// LDS goal tables of the env (2 x (NPAD + 4) rows of 4 floats), after the obs / exchange tiles, then the env's
-// scenario record (SC_WORDS words, padded to 32; the flavor-B step kernel's copy for scen_step_lane)
-template <int NPAD>
-constexpr int scen_stride() { return 2 * (NPAD + 4) * 4 + 32; }
-__device__ __forceinline__ float* scen_tab(float* lds, const KP& kp, int slots) {
-    return lds + slots * kp.obs_dim + slots * 8 + 64;
-}
+static_assert(SC_WORDS <= 32, "the scenario record's slot after the goal tables (qs_common.h scen_stride)");
 
 }  // namespace qs

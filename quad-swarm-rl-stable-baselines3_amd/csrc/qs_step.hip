@@ -174,7 +174,7 @@ static int validate(const qs_config* c) {
         if (c->n_cameras < 1 || c->n_cameras > 8) return fail(QS_E_INVALID, "n_cameras must be 1..8");
         // envs of more than 64 drones (multi-wave workgroups) select their neighbours by register insertion
         // (qs_flavor_a.h neighbor_obs_wide)
-        if (c->num_agents > 64 && c->neighbor_obs != QS_NEIGHBOR_NONE && c->k_neighbors > QS_A_KMAX)
+        if (c->num_agents > 64 && c->neighbor_obs != QS_NEIGHBOR_NONE && c->k_neighbors > qs::QS_A_KMAX)
             return fail(QS_E_UNSUPPORTED, "flavor A with more than 64 drones: k_neighbors must be <= QS_A_KMAX (16)");
     }
     if (c->neighbor_obs != QS_NEIGHBOR_NONE && (c->k_neighbors < 1 || c->k_neighbors > c->num_agents - 1))
@@ -192,7 +192,7 @@ static int npad_of(int n);
 // a gfx950 workgroup may allocate the CU's whole 160 KB of LDS (64-drone envs with all 63 neighbours visible
 // stage 64 rows of 396 floats)
 static constexpr size_t QS_LDS_MAX = 160 * 1024;
-static size_t shm_bytes(const qs_config& c, int obs_dim, int npad, bool step, int qb = QS_QB, int qa = QS_QA);
+static size_t shm_bytes(const qs::KP& kp, int npad, bool step, int qb = QS_QB, int qa = QS_QA);
 static int neighbor_dim(int t);
 
 // pillar slots per env: the configured count, or the largest domain-randomisation choice
@@ -484,9 +484,9 @@ extern "C" int qs_config_default_a(qs_config* c, int32_t num_envs, int32_t num_a
 }
 
 static int check_lds(const qs_config* c) {
-    const qs_layout L = make_layout(c);
+    const qs::KP kp = make_kp(c, make_layout(c));
     const int np = npad_of(c->num_agents);
-    if (shm_bytes(*c, L.obs_dim, np, true) > QS_LDS_MAX || shm_bytes(*c, L.obs_dim, np, false) > QS_LDS_MAX)
+    if (shm_bytes(kp, np, true) > QS_LDS_MAX || shm_bytes(kp, np, false) > QS_LDS_MAX)
         return fail(QS_E_UNSUPPORTED, "observation / obstacle tiles exceed the 160 KB of LDS of a workgroup");
     return QS_OK;
 }
@@ -500,39 +500,23 @@ extern "C" int qs_layout_query(const qs_config* c, qs_layout* out) {
     return QS_OK;
 }
 
-// Step launches give every drone Q lanes (qs::StepGeo for flavor B: QS_QB, qs::StepGeoA for A: QS_QA; fewer
-// when an env would not fit a wave); resets one lane.  Specialised kernels may be compiled with another Q
-// (qs_handle::qb / qa).
-// flavor B (qs::StepGeo): QS_QW sub-lanes for the multi-wave 64 / 128-drone envs; flavor A (qs::StepGeoA): an
-// env of up to 64 drones stays inside one wave, a 128-drone env takes QS_QW sub-lanes over 4 waves
-static int step_lanes_per_drone(int npad, int q, bool flavor_a = false) {
-    return npad * q <= 64 ? q : ((npad >= 64 && !flavor_a) || npad > 64 ? QS_QW : 64 / npad);
+// The launch geometry and LDS map of a kernel are the ones it indexes by (qs_common.h step_geo / reset_geo / lds_map,
+// from the same KP fields).  Specialised step kernels may be compiled with another Q (qs_handle::qb / qa).
+static qs::Geo launch_geo(const qs::KP& kp, int npad, bool step, int qb, int qa) {
+    const bool a = kp.flavor == QS_FLAVOR_A;
+    return step ? qs::step_geo(npad, a ? qa : qb, a) : qs::reset_geo(npad);
 }
-static_assert(qs::StepGeo<8>::Q == QS_QB && qs::StepGeo<32>::Q == 64 / 32 && qs::StepGeo<64>::Q == QS_QW &&
-              qs::StepGeo<128>::Q == QS_QW && qs::StepGeo<128>::WGS == 128 * QS_QW && qs::StepGeoA<8>::Q == QS_QA &&
-              qs::StepGeoA<32>::Q == 2 && qs::StepGeoA<64>::Q == 1 && qs::StepGeoA<128>::Q == QS_QW &&
-              qs::StepGeoA<128>::WGS == 128 * QS_QW && qs::ResetGeoA<128>::WGS == 128 && qs::ResetGeoA<8>::EPB == 8,
-              "step_lanes_per_drone");
-// threads per workgroup: one wave, or (128-drone envs) the env's lanes
-static int block_threads(const qs_config& c, int npad, bool step, int qb = QS_QB, int qa = QS_QA) {
-    const int q = !step ? 1 : step_lanes_per_drone(npad, c.flavor == QS_FLAVOR_A ? qa : qb, c.flavor == QS_FLAVOR_A);
-    return npad * q > 64 ? npad * q : 64;
+static int block_threads(const qs::KP& kp, int npad, bool step, int qb = QS_QB, int qa = QS_QA) {
+    return launch_geo(kp, npad, step, qb, qa).WGS;
 }
-static int envs_per_block(const qs_config& c, int npad, bool step, int qb = QS_QB, int qa = QS_QA) {
-    const int q = !step ? 1 : step_lanes_per_drone(npad, c.flavor == QS_FLAVOR_A ? qa : qb, c.flavor == QS_FLAVOR_A);
-    return block_threads(c, npad, step, qb, qa) / (npad * q);
+static int envs_per_block(const qs::KP& kp, int npad, bool step, int qb = QS_QB, int qa = QS_QA) {
+    return launch_geo(kp, npad, step, qb, qa).EPB;
 }
-
-// dynamic LDS of a launch with `slots` drone rows per workgroup: obs tile + neighbour exchange tile
-// + 64 words (flavor-A flags) + obstacle tiles and per-env reset scratch (qs_flavor_b.h obst_tile)
-static size_t shm_bytes(const qs_config& c, int obs_dim, int npad, bool step, int qb, int qa) {
-    const size_t epb = (size_t)envs_per_block(c, npad, step, qb, qa), slots = epb * (size_t)npad;
-    size_t b = sizeof(float) * slots * (size_t)obs_dim + sizeof(float) * slots * 8 + sizeof(float) * 64;
-    if (c.use_obstacles) b += epb * (sizeof(float) * 2 * (size_t)obst_slots(&c) + (size_t)qs::QS_OBST_SCRATCH);
-    const bool tables = c.use_obstacles ? c.scenario >= QS_SCEN_O_SWAP_GOALS
-                                        : (c.scenario >= QS_SCEN_MIX && c.scenario <= QS_SCEN_RUN_AWAY);
-    if (tables) b += epb * sizeof(float) * (2 * ((size_t)npad + 4) * 4 + 32);   // goal tables (qs::scen_stride)
-    return b;
+static size_t shm_bytes(const qs::KP& kp, int npad, bool step, int qb, int qa) {
+    const qs::Geo g = launch_geo(kp, npad, step, qb, qa);
+    const bool obst = kp.obst != 0;
+    const qs::LdsMap m = qs::lds_map(g, kp.obs_dim, kp.M, obst);
+    return sizeof(float) * (size_t)qs::lds_words(m, g, npad, qs::scen_tables(obst, kp.scen_b));
 }
 
 static int npad_of(int n) {
@@ -655,9 +639,9 @@ static int launch(qs_handle* h, bool step, const float* act, const uint8_t* mask
     b.act = act;
     b.mask = mask;
     const qs::KP* kpd = (const qs::KP*)((char*)h->ws + h->lay.params);
-    const int epb = envs_per_block(h->cfg, h->npad, step, h->qb, h->qa);
-    const dim3 grid((unsigned)((h->kp.E + epb - 1) / epb)), block((unsigned)block_threads(h->cfg, h->npad, step, h->qb, h->qa));
-    const size_t shm = shm_bytes(h->cfg, h->kp.obs_dim, h->npad, step, h->qb, h->qa);
+    const int epb = envs_per_block(h->kp, h->npad, step, h->qb, h->qa);
+    const dim3 grid((unsigned)((h->kp.E + epb - 1) / epb)), block((unsigned)block_threads(h->kp, h->npad, step, h->qb, h->qa));
+    const size_t shm = shm_bytes(h->kp, h->npad, step, h->qb, h->qa);
     const bool a = h->cfg.flavor == QS_FLAVOR_A, ob = h->kp.obst != 0;
     // the flavor-B step kernel runs the replay wrapper in its tail (qs_replay.h); rb.ri == NULL: replay off
     const qs::RArgs* ra = rargs_of(h);
@@ -1266,7 +1250,7 @@ extern "C" int qs_specialize(qs_handle* h, int enable) {
     QS_HIP(use_device(h));
     int qb, qa;
     jit_lanes(&qb, &qa);
-    if (shm_bytes(h->cfg, h->lay.obs_dim, h->npad, true, qb, qa) > QS_LDS_MAX)
+    if (shm_bytes(h->kp, h->npad, true, qb, qa) > QS_LDS_MAX)
         return fail(QS_E_UNSUPPORTED, "QS_QB / QS_QA geometry exceeds the 160 KB of LDS of a workgroup");
     std::string rn;
     const std::string key = std::to_string(h->device) + "|" + kernel_names(&h->cfg, h->kp, h->npad, &rn) + "|" +

@@ -42,10 +42,7 @@ for s in "$@"; do
       rm -f gpurun_out/kt_*/*/*kernel_trace.csv gpurun_out/kt_*/*kernel_trace.csv
       ;;
     benchn64) step bench_n64 300 python bench.py --config n64 --steps 1000 --full --cpu-seconds 5 --e2e-iters 0 ;;
-    abstatsa)
-      step a8_nost 300 python bench.py --config a8 --steps 1000 --no-cpu-baseline --e2e-iters 0 --no-episode-stats
-      CONFIG=a8 STEPS=1000 step a8_ab 600 bash tools/ab_jit.sh base: nocol:-DQS_DIAG_A_NOCOL
-      ;;
+    abstatsa) step a8_nost 300 python bench.py --config a8 --steps 1000 --no-cpu-baseline --e2e-iters 0 --no-episode-stats ;;
     statsa)
       step stats_a 600 python -u -m pytest tests/test_gpu_stats.py tests/test_gpu_parity_a.py -v --timeout 200 --timeout-method thread
       step a8_after 300 python bench.py --config a8 --steps 1000 --no-cpu-baseline --e2e-iters 0
@@ -139,11 +136,6 @@ for s in "$@"; do
       step prof_${C}_sq 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_INSTS_LDS -d gpurun_out/prof_${C}_sq -o s --output-format csv -- python bench.py --config $C --steps 100 --warmup 10 --no-cpu-baseline --graph 0 --e2e-iters 0
       step prof_${C}_flops 300 timeout -s KILL 240 rocprofv3 --pmc SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_FLOPS_FP32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_CVT SQ_WAVES -d gpurun_out/prof_${C}_flops -o fl --output-format csv -- python bench.py --config $C --steps 100 --warmup 10 --no-cpu-baseline --graph 0 --e2e-iters 0
       rm -f gpurun_out/prof_${C}_*/*kernel_trace.csv gpurun_out/prof_${C}_*/*/*kernel_trace.csv
-      ;;
-    sel2)      # QS_NBR_SELECT2 on 32-drone envs: bitwise digest A/B + timing A/B
-      step sel2_dig0 200 python tools/bitwise_ab.py c5 60
-      step sel2_dig1 200 env QS_JIT_OPTS=-DQS_NBR_SELECT2=1 python tools/bitwise_ab.py c5 60
-      CONFIG=c5 STEPS=2000 step sel2_ab 600 bash tools/ab_jit.sh base: sel2:-DQS_NBR_SELECT2=1 base2: sel2b:-DQS_NBR_SELECT2=1
       ;;
     stamps) step stamps 300 python tools/phase_stamps.py ;;
     profpol)   # the rollout policy's kernels (C3): kernel trace + one PMC pass of MFMA counters on the fused encoders
