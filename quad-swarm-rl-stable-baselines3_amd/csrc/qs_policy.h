@@ -27,6 +27,14 @@
 // to the accumulators as they are written back to LDS.  fp32 throughout (the reference trains in fp32);
 // tanh is 1 - 2 / (exp(2x) + 1) on the hardware exp2 / rcp (absolute error < 3e-7 against tanhf).
 // Roofline: the matrix cores (157 TF fp32 dense): 5 H^2 + 32 H MACs per neighbour row and tower.
+//
+// Sources of the policy translation unit (qs_policy_api.hip is its C ABI):
+//   qs_policy.h       : block geometry, the fp32 layer, and every piece of the forward that does not depend on the
+//                       contraction (row gather, accumulator layout, acc_from_P, score_partials, score_softmax,
+//                       agent_sum, tanh_bias4, the A3 table); the two fp32 kernels
+//   qs_policy_x3.h    : the split-f16 tile and layer, attn_embed_x3_body (the rollout's and the update's embedding),
+//                       the rollout's attn_pool_x3_kernel, the feed_forward linear_tanh_x3_kernel
+//   qs_policy_train.h : the update's attn_pool_train_x3_kernel (the forward with saves), the backward, dW, statistics
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
@@ -166,7 +174,19 @@ __device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float
 __device__ __forceinline__ float4 f4_tanh(float4 a) {
     return make_float4(tanh_fast(a.x), tanh_fast(a.y), tanh_fast(a.z), tanh_fast(a.w));
 }
+__device__ __forceinline__ float4 f4_scale(float4 v, float s) { return make_float4(s * v.x, s * v.y, s * v.z, s * v.w); }
 __device__ __forceinline__ float4 acc4(const f32x16& a, int g) { return make_float4(a[4 * g], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3]); }
+__device__ __forceinline__ void acc4_set(f32x16& a, int g, float4 v) {
+    a[4 * g] = v.x; a[4 * g + 1] = v.y; a[4 * g + 2] = v.z; a[4 * g + 3] = v.w;
+}
+__device__ __forceinline__ float4 lds4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float4 ld4g(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4g(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+// tanh(acc[4g .. 4g + 3] * inv + b): four consecutive output columns of an accumulator tile
+__device__ __forceinline__ float4 tanh_bias4(const f32x16& a, int g, float inv, float4 b) {
+    return make_float4(tanh_fast(fmaf(a[4 * g], inv, b.x)), tanh_fast(fmaf(a[4 * g + 1], inv, b.y)),
+                       tanh_fast(fmaf(a[4 * g + 2], inv, b.z)), tanh_fast(fmaf(a[4 * g + 3], inv, b.w)));
+}
 
 // Y[i][n0 .. n0 + 3] = tanh(acc + bias4(i, n0)) into LDS
 template <int H, typename Bias4>
@@ -184,7 +204,6 @@ __device__ __forceinline__ void store_tanh(float* Y, const f32x16 (&acc)[RT][Geo
             }
     }
 }
-__device__ __forceinline__ float4 lds4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 // score = tanh(acc * inv + b_a2) . a3 straight from the a2 layer's accumulators (a2 itself is never stored): this
 // lane's part of row i's dot, summed with the other lane half (same row, other columns); SCP[wave][i] = the wave's
@@ -201,7 +220,7 @@ __device__ __forceinline__ void score_partials(const f32x16 (&acc)[RT][Geo<H>::C
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int n0 = acc_n0<H>(wave, c, g, lane);
-                const float4 b = lds4(ba2 + n0), w = lds4(a3 + n0);
+                const float4 b = lds4(ba2 + n0), w = lds4(a3 + n0);   // (each tanh feeds its fma: not tanh_bias4)
                 p = fmaf(tanh_fast(fmaf(acc[rt][c][4 * g], inv, b.x)), w.x, p);
                 p = fmaf(tanh_fast(fmaf(acc[rt][c][4 * g + 1], inv, b.y)), w.y, p);
                 p = fmaf(tanh_fast(fmaf(acc[rt][c][4 * g + 2], inv, b.z)), w.z, p);
@@ -209,6 +228,75 @@ __device__ __forceinline__ void score_partials(const f32x16 (&acc)[RT][Geo<H>::C
             }
         p += __shfl_xor(p, 32);
         if (lane < 32) SCP[wave * MROWS + acc_i(rt, lane)] = p;
+    }
+}
+
+// The pooling kernels' accumulators start at scale * P[j % B], the per-agent half of attention_mlp[0] with its bias
+// (scale: 1, or the split products' s_x s_w), so that P's latency overlaps the e2 rows'.  Loaded unconditionally
+// (row 0 stands in for an unused row) and zeroed by a product: a conditional load (or a select the compiler sinks
+// back into a branch) costs a branch + a full wait per load, 16 serial HBM latencies.
+template <int H>
+__device__ __forceinline__ void acc_from_P(f32x16 (&acc)[RT][Geo<H>::CT], const float* __restrict__ P, float scale,
+                                           long row0, int MU, long R, int B, int wave, int lane) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        const int i = acc_i(rt, lane);
+        const int j = (int)row0 + i;
+        const bool ok = i < MU && j < R;
+        const float okf = ok ? 1.f : 0.f;
+        const float* pr = P + (size_t)(ok ? j % B : 0) * H;
+#pragma unroll
+        for (int c = 0; c < Geo<H>::CT; ++c)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                acc4_set(acc[rt][c], g, f4_scale(f4_scale(ld4g(pr + acc_n0<H>(wave, c, g, lane)), okf), scale));
+    }
+}
+
+// score = (the four waves' score_partials) + b_a3 into SC, then w = softmax over each agent's K rows into WT.  Call
+// after the barrier that completes SCP; WT is complete after the caller's next barrier.
+__device__ __forceinline__ void score_softmax(float* SC, const float* SCP, float* WT, float b_a3, int AB, int K, int tid) {
+    if (tid < MROWS) SC[tid] = ((SCP[tid] + SCP[MROWS + tid]) + (SCP[2 * MROWS + tid] + SCP[3 * MROWS + tid])) + b_a3;
+    __syncthreads();
+    if (tid < AB) {
+        const int base = tid * K;
+        float m = SC[base];
+        for (int k = 1; k < K; ++k) m = fmaxf(m, SC[base + k]);
+        float s = 0.f;
+        for (int k = 0; k < K; ++k) {
+            const float x = expf(SC[base + k] - m);
+            WT[base + k] = x;
+            s += x;
+        }
+        for (int k = 0; k < K; ++k) WT[base + k] = WT[base + k] / s;
+    }
+}
+
+// dst[agent] = scale * (the agent's K rows of the LDS tile src (row stride ld), summed in k order from 0) for the
+// block's AB agents, one column per thread.  (scale 1 for a plain sum; 1 / K for torch's mean: the sum times 1 / K.)
+// The two rollout x3 kernels keep float4-wide sums of their own (qs_policy_x3.h).
+template <int H>
+__device__ __forceinline__ void agent_sum(const float* src, int ld, int AB, int K, int B, long row0, float* dst,
+                                          float scale, int tid) {
+    for (int e = tid; e < AB * H; e += NTHR) {
+        const int a = e / H, n = e - a * H;
+        const long agent = row0 / K + a;
+        if (agent >= B) continue;
+        const float* rows = src + (a * K) * ld + n;
+        float s = 0.f;
+        for (int k = 0; k < K; ++k) s += rows[k * ld];
+        dst[agent * H + n] = s * scale;
+    }
+}
+
+// the pooling kernels' LDS table A3: attention_mlp[4].weight, then b_a2, b_v1, b_v2 (H floats each)
+template <int H>
+__device__ __forceinline__ void load_a3_table(float* A3, const qs_attn_tower& t, int tid) {
+    for (int n = tid; n < H; n += NTHR) {
+        A3[n] = t.w_a3[n];
+        A3[H + n] = t.b_a2[n];
+        A3[2 * H + n] = t.b_v1[n];
+        A3[3 * H + n] = t.b_v2[n];
     }
 }
 
@@ -263,16 +351,7 @@ __global__ __launch_bounds__(NTHR, 2) void attn_embed_kernel(const float* __rest
         if (r < MU && j < R)
             reinterpret_cast<float4*>(t.e2 + j * H)[c4] = *reinterpret_cast<const float4*>(X + r * LD + 4 * c4);
     }
-    const float inv = 1.f / (float)K;   // torch's mean: the sum times 1 / K
-    for (int e = tid; e < AB * H; e += NTHR) {
-        const int a = e / H, n = e - a * H;
-        const long agent = row0 / K + a;
-        if (agent < B) {
-            float s = 0.f;
-            for (int k = 0; k < K; ++k) s += X[(a * K + k) * LD + n];
-            t.e_mean[agent * H + n] = s * inv;
-        }
-    }
+    agent_sum<H>(X, LD, AB, K, B, row0, t.e_mean, 1.f / (float)K, tid);
     QS_STAMP(5);
     QS_RTSTAMP(13);
     QS_STAMP_FLUSH();
@@ -289,7 +368,7 @@ __device__ __forceinline__ void load_rows(float* X, const float* __restrict__ sr
         const long j = row0 + r;
         const bool ok = r < MU && j < R;
         const float okf = ok ? 1.f : 0.f;
-        v[u] = reinterpret_cast<const float4*>(src + (ok ? j : 0) * H)[c4];   // unconditional (see the P loads)
+        v[u] = reinterpret_cast<const float4*>(src + (ok ? j : 0) * H)[c4];   // unconditional (see acc_from_P)
         v[u] = make_float4(v[u].x * okf, v[u].y * okf, v[u].z * okf, v[u].w * okf);
     }
 #pragma unroll
@@ -316,35 +395,11 @@ __global__ __launch_bounds__(NTHR, 2) void attn_pool_kernel(int B, int K, Towers
     QS_STAMP_DECL
     QS_RTSTAMP(12);
     QS_STAMP(0);
-    for (int n = tid; n < H; n += NTHR) {
-        A3[n] = t.w_a3[n];
-        A3[H + n] = t.b_a2[n];
-        A3[2 * H + n] = t.b_v1[n];
-        A3[3 * H + n] = t.b_v2[n];
-    }
+    load_a3_table<H>(A3, t, tid);
     // attention_mlp: a1 = tanh(e2 A_e^T + P[j % B]); the per-agent half (with its bias) is the accumulators'
     // start, loaded with the block's e2 rows so that both latencies overlap
     f32x16 acc[RT][CT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-        const int i = acc_i(rt, lane);
-        const int j = (int)row0 + i;
-        const bool ok = i < MU && j < R;
-        const float okf = ok ? 1.f : 0.f;
-        const float* pr = t.P + (size_t)(ok ? j % B : 0) * H;
-#pragma unroll
-        for (int c = 0; c < CT; ++c)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                // loaded unconditionally (row 0 stands in for an unused row) and zeroed by a product: a
-                // conditional load (or a select the compiler sinks back into a branch) costs a branch + a full
-                // wait per load, 16 serial HBM latencies
-                float4 v = *reinterpret_cast<const float4*>(pr + acc_n0<H>(wave, c, g, lane));
-                v = make_float4(v.x * okf, v.y * okf, v.z * okf, v.w * okf);
-                acc[rt][c][4 * g] = v.x; acc[rt][c][4 * g + 1] = v.y;
-                acc[rt][c][4 * g + 2] = v.z; acc[rt][c][4 * g + 3] = v.w;
-            }
-    }
+    acc_from_P<H>(acc, t.P, 1.f, row0, MU, R, B, wave, lane);
     load_rows<H>(X, t.e2, row0, MU, R, tid);
     __syncthreads();
     QS_STAMP(1);
@@ -361,20 +416,7 @@ __global__ __launch_bounds__(NTHR, 2) void attn_pool_kernel(int B, int K, Towers
     score_partials<H>(acc, 1.f, A3, A3 + H, SCP, wave, lane);
     __syncthreads();
     QS_STAMP(5);
-    if (tid < MROWS) SC[tid] = ((SCP[tid] + SCP[MROWS + tid]) + (SCP[2 * MROWS + tid] + SCP[3 * MROWS + tid])) + t.b_a3;
-    __syncthreads();
-    if (tid < AB) {   // softmax over the agent's K rows
-        const int base = tid * K;
-        float m = SC[base];
-        for (int k = 1; k < K; ++k) m = fmaxf(m, SC[base + k]);
-        float s = 0.f;
-        for (int k = 0; k < K; ++k) {
-            const float x = expf(SC[base + k] - m);
-            WT[base + k] = x;
-            s += x;
-        }
-        for (int k = 0; k < K; ++k) WT[base + k] = WT[base + k] / s;
-    }
+    score_softmax(SC, SCP, WT, t.b_a3, AB, K, tid);
     // neighbor_value_mlp on the e2 rows again (L2 / Infinity Cache): h1 -> tile, h -> weighted into the tile
     load_rows<H>(X, t.e2, row0, MU, R, tid);
     __syncthreads();
@@ -398,19 +440,11 @@ __global__ __launch_bounds__(NTHR, 2) void attn_pool_kernel(int B, int K, Towers
             for (int g = 0; g < 4; ++g) {
                 const int n0 = acc_n0<H>(wave, c, g, lane);
                 const float4 h = f4_tanh(f4_add(acc4(acc[rt][c], g), lds4(A3 + 3 * H + n0)));
-                *reinterpret_cast<float4*>(X + i * LD + n0) = make_float4(wi * h.x, wi * h.y, wi * h.z, wi * h.w);
+                *reinterpret_cast<float4*>(X + i * LD + n0) = f4_scale(h, wi);
             }
     }
     __syncthreads();
-    for (int e = tid; e < AB * H; e += NTHR) {
-        const int a = e / H, n = e - a * H;
-        const long agent = row0 / K + a;
-        if (agent < B) {
-            float s = 0.f;
-            for (int k = 0; k < K; ++k) s += X[(a * K + k) * LD + n];
-            t.out[agent * H + n] = s;
-        }
-    }
+    agent_sum<H>(X, LD, AB, K, B, row0, t.out, 1.f, tid);
     QS_STAMP(10);
     QS_RTSTAMP(13);
     QS_STAMP_FLUSH();

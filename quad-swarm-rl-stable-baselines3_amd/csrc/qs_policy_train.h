@@ -1,5 +1,8 @@
 // qs_policy_train.h -- the PPO update's attention neighbour encoder on the split-f16 matrix cores: the forward with
 // the activations the backward needs saved, and the backward's two row-block chains (the update side).
+// Here: the row-scaled staging, attn_embed_train_x3_kernel (a wrapper of qs_policy_x3.h's embedding body),
+// attn_pool_train_x3_kernel, the two backward kernels, dW / dW0 and the column statistics.  (Which header holds what:
+// qs_policy.h's header.)
 //
 // QuadNeighborhoodEncoderAttention (swarm_rl/models/quad_multi_model.py:44-101) as qs_policy.h writes it, per
 // neighbour row j (row j = agent j / K, neighbour j % K; self / e_mean of agent j % B -- the reference's pairing):
@@ -68,10 +71,7 @@ __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, dppf<0x128>(v));
     return fmaxf(fmaxf(rdl(v, 0), rdl(v, 16)), fmaxf(rdl(v, 32), rdl(v, 48)));
 }
-__device__ __forceinline__ float4 ld4g(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4g(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float absmax4(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
-__device__ __forceinline__ float4 f4_scale(float4 v, float s) { return make_float4(s * v.x, s * v.y, s * v.z, s * v.w); }
 __device__ __forceinline__ float4 f4_dtanh(float4 g, float4 t) {   // g (1 - t^2)
     return make_float4(g.x * (1.f - t.x * t.x), g.y * (1.f - t.y * t.y), g.z * (1.f - t.z * t.z), g.w * (1.f - t.w * t.w));
 }
@@ -224,55 +224,18 @@ __device__ __forceinline__ void stage_acc_scaled(const TileX3& X, f32x16 (&acc)[
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// forward with saves: attn_embed_x3_kernel + e1; attn_pool_x3_kernel + a1, a2, v1, h, w (qs_policy_x3.h, same math)
+// forward with saves.  The embedding is the rollout's body (qs_policy_x3.h attn_embed_x3_body) with e1 saved.  The
+// pooling is its own phase sequence next to attn_pool_x3_kernel, built from qs_policy.h's helpers; it differs on purpose:
+//   - a1, a2, v1, h are stored as they are formed and w after one more barrier (WT complete before tr.w reads it);
+//   - a2 is formed twice, once to store and once inside score_partials (the rollout never materialises it);
+//   - the final per-agent sum is scalar: float4-wide as in the rollout costs 4 spilled registers here.
+// A merged body was tried and put 6 spilled VGPRs into attn_pool_x3_kernel<256>.
 // ------------------------------------------------------------------------------------------------------------------
 template <int H>
 __global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_embed_train_x3_kernel(
     const float* __restrict__ obs, int stride, int so, int off, int B, int K, int nd, Towers tw, Trains trs) {
-    constexpr int LDH = GeoX3<H>::LDH, LD0 = GeoX3<KD0>::LDH, CT = Geo<H>::CT;
-    extern __shared__ float4 smem4[];
-    _Float16* xh = reinterpret_cast<_Float16*>(smem4);
-    const TileX3 X{xh, xh + MROWS * LDH, LDH};
-    const TileX3 X0{xh + 2 * MROWS * LDH, xh + 2 * MROWS * LDH + MROWS * LD0, LD0};
-    float* BI = reinterpret_cast<float*>(xh + 2 * MROWS * LDH + 2 * MROWS * LD0);
-    const qs_attn_tower& t = tw.t[blockIdx.y];
-    const qs_attn_train& tr = trs.t[blockIdx.y];
-    const int AB = MROWS / K, MU = AB * K;
-    const long R = (long)B * K, row0 = (long)blockIdx.x * MU;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    QS_STAMP_DECL
-    QS_RTSTAMP(12);
-    QS_STAMP(0);
-    for (int n = tid; n < H; n += NTHR) {
-        BI[n] = t.b_e1[n];
-        BI[H + n] = t.b_e2[n];
-    }
-    gather_rows0(obs, stride, so, off, B, K, nd, row0, MU, R, tid, [&](int r, int c, float v) { X0.put(r, c, X3_SIN * v); });
-    __syncthreads();
-    QS_STAMP(1);
-    f32x16 acc[RT][CT];
-    mfma_layer_x3<H, KD0, true, false>(X0, reinterpret_cast<const uint4*>(t.w_e1p), acc, wave, lane);
-    QS_STAMP(2);
-    const auto qe2 = mfma_prefetch_x3<H>(reinterpret_cast<const uint4*>(t.w_e2p), wave, lane);   // ahead of e1's stores
-    store_tanh_x3<H>(X, acc, 1.f / (X3_SIN * X3_SW), wave, lane,
-                     [&](int i, int n0) {
-                         return (i < MU && row0 + i < R) ? lds4(BI + n0) : make_float4(0.f, 0.f, 0.f, 0.f);
-                     },
-                     [&](int i, int n0, float4 y) {
-                         if (i < MU && row0 + i < R) st4g(tr.e1 + (row0 + i) * H + n0, y);
-                     });
-    __syncthreads();
-    QS_STAMP(3);
-    mfma_layer_x3<H, H, true, true>(X, reinterpret_cast<const uint4*>(t.w_e2p), acc, wave, lane, qe2);
-    __syncthreads();
-    QS_STAMP(4);
-    embed_e2_epilogue<H>(acc, BI + H, t.e2, t.e_mean, smem4, row0, MU, R, B, K, AB, wave, lane, tid);
-    QS_STAMP(5);
-    QS_STAMP(6);
-    QS_RTSTAMP(13);
-    if (blockIdx.y == 0) QS_STAMP_FLUSH();
+    attn_embed_x3_body<H, true>(obs, stride, so, off, B, K, nd, tw.t[blockIdx.y], trs.t[blockIdx.y].e1);
 }
-
 
 template <int H>
 __global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_pool_train_x3_kernel(
@@ -293,30 +256,10 @@ __global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2)))
     QS_STAMP_DECL
     QS_RTSTAMP(12);
     QS_STAMP(0);
-    for (int n = tid; n < H; n += NTHR) {
-        A3[n] = t.w_a3[n];
-        A3[H + n] = t.b_a2[n];
-        A3[2 * H + n] = t.b_v1[n];
-        A3[3 * H + n] = t.b_v2[n];
-    }
+    load_a3_table<H>(A3, t, tid);
     auto okrow = [&](int i) { return i < MU && row0 + i < R; };
     f32x16 acc[RT][CT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-        const int i = acc_i(rt, lane);
-        const int j = (int)row0 + i;
-        const float okf = okrow(i) ? 1.f : 0.f;
-        const float* pr = t.P + (size_t)(okrow(i) ? j % B : 0) * H;
-#pragma unroll
-        for (int c = 0; c < CT; ++c)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float4 v = *reinterpret_cast<const float4*>(pr + acc_n0<H>(wave, c, g, lane));
-                v = make_float4(v.x * okf, v.y * okf, v.z * okf, v.w * okf);
-                acc[rt][c][4 * g] = SS * v.x; acc[rt][c][4 * g + 1] = SS * v.y;
-                acc[rt][c][4 * g + 2] = SS * v.z; acc[rt][c][4 * g + 3] = SS * v.w;
-            }
-    }
+    acc_from_P<H>(acc, t.P, SS, row0, MU, R, B, wave, lane);
     load_rows_x3<H>(X, t.e2, row0, MU, R, tid);
     __syncthreads();
     QS_STAMP(1);
@@ -341,30 +284,14 @@ __global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int n0 = acc_n0<H>(wave, c, g, lane);
-                const float4 b = lds4(A3 + H + n0);
-                st4g(tr.a2 + (row0 + i) * H + n0,
-                     make_float4(tanh_fast(fmaf(acc[rt][c][4 * g], iSS, b.x)), tanh_fast(fmaf(acc[rt][c][4 * g + 1], iSS, b.y)),
-                                 tanh_fast(fmaf(acc[rt][c][4 * g + 2], iSS, b.z)), tanh_fast(fmaf(acc[rt][c][4 * g + 3], iSS, b.w))));
+                st4g(tr.a2 + (row0 + i) * H + n0, tanh_bias4(acc[rt][c], g, iSS, lds4(A3 + H + n0)));
             }
     }
     float* SCP = A3 + 4 * H;
     score_partials<H>(acc, iSS, A3, A3 + H, SCP, wave, lane);
     __syncthreads();
     QS_STAMP(5);
-    if (tid < MROWS) SC[tid] = ((SCP[tid] + SCP[MROWS + tid]) + (SCP[2 * MROWS + tid] + SCP[3 * MROWS + tid])) + t.b_a3;
-    __syncthreads();
-    if (tid < AB) {
-        const int base = tid * K;
-        float m = SC[base];
-        for (int k = 1; k < K; ++k) m = fmaxf(m, SC[base + k]);
-        float s = 0.f;
-        for (int k = 0; k < K; ++k) {
-            const float x = expf(SC[base + k] - m);
-            WT[base + k] = x;
-            s += x;
-        }
-        for (int k = 0; k < K; ++k) WT[base + k] = WT[base + k] / s;
-    }
+    score_softmax(SC, SCP, WT, t.b_a3, AB, K, tid);
     __syncthreads();   // WT complete (the tile is free since the score barrier)
     if (tid < MU && row0 + tid < R) tr.w[row0 + tid] = WT[tid];
     QS_STAMP(6);
@@ -389,24 +316,14 @@ __global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int n0 = acc_n0<H>(wave, c, g, lane);
-                const float4 b = lds4(A3 + 3 * H + n0);
-                const float4 h = make_float4(tanh_fast(fmaf(acc[rt][c][4 * g], iSS, b.x)), tanh_fast(fmaf(acc[rt][c][4 * g + 1], iSS, b.y)),
-                                             tanh_fast(fmaf(acc[rt][c][4 * g + 2], iSS, b.z)), tanh_fast(fmaf(acc[rt][c][4 * g + 3], iSS, b.w)));
+                const float4 h = tanh_bias4(acc[rt][c], g, iSS, lds4(A3 + 3 * H + n0));
                 if (okrow(i)) st4g(tr.h + (row0 + i) * H + n0, h);
-                *reinterpret_cast<float4*>(Y + i * LDY + n0) = make_float4(wi * h.x, wi * h.y, wi * h.z, wi * h.w);
+                *reinterpret_cast<float4*>(Y + i * LDY + n0) = f4_scale(h, wi);
             }
     }
     __syncthreads();
     QS_STAMP(10);
-    for (int e = tid; e < AB * H; e += NTHR) {   // (float4-wide as the rollout kernel: 4 spilled registers here)
-        const int a = e / H, n = e - a * H;
-        const long agent = row0 / K + a;
-        if (agent < B) {
-            float s = 0.f;
-            for (int k = 0; k < K; ++k) s += Y[(a * K + k) * LDY + n];
-            t.out[agent * H + n] = s;
-        }
-    }
+    agent_sum<H>(Y, LDY, AB, K, B, row0, t.out, 1.f, tid);   // (float4-wide as the rollout kernel: 4 spilled registers here)
     QS_STAMP(11);
     QS_RTSTAMP(13);
     if (blockIdx.y == 0) QS_STAMP_FLUSH();

@@ -1,6 +1,7 @@
 // qs_policy_x3.h -- the fused attention-encoder forward of qs_policy.h with every fp32 product split over the
 // f16 matrix cores (precision QS_ATTN_X3).
 //
+// (What lives in which of the policy headers: qs_policy.h's header.)
 // Same function, same two kernels, same block structure (64 neighbour rows per block, 4 waves, wave w owning
 // output columns [w H/4, (w+1) H/4)); what changes is the contraction.  Each fp32 operand x is carried as two
 // f16 values, hi = f16(s x) and lo = f16(s x - hi) with a power-of-two scale s (activations 2^8, raw obs 2^4,
@@ -188,13 +189,9 @@ __device__ __forceinline__ void store_tanh_x3(const TileX3& Y, const f32x16 (&ac
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int n0 = acc_n0<H>(wave, c, g, lane);
-                const float4 b = bias4(i, n0);
-                const float4 y = make_float4(tanh_fast(fmaf(acc[rt][c][4 * g], inv, b.x)),
-                                             tanh_fast(fmaf(acc[rt][c][4 * g + 1], inv, b.y)),
-                                             tanh_fast(fmaf(acc[rt][c][4 * g + 2], inv, b.z)),
-                                             tanh_fast(fmaf(acc[rt][c][4 * g + 3], inv, b.w)));
+                const float4 y = tanh_bias4(acc[rt][c], g, inv, bias4(i, n0));
                 out(i, n0, y);
-                Y.put4(i, n0, make_float4(X3_SX * y.x, X3_SX * y.y, X3_SX * y.z, X3_SX * y.w));   // (exact: 2^8)
+                Y.put4(i, n0, f4_scale(y, X3_SX));   // (exact: 2^8)
             }
     }
 }
@@ -218,16 +215,13 @@ __device__ __forceinline__ void embed_e2_epilogue(const f32x16 (&acc)[RT][Geo<H>
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int n0 = acc_n0<H>(wave, c, g, lane);
-                const float4 b = lds4(bias + n0);
-                const float4 y = make_float4(tanh_fast(fmaf(acc[rt][c][4 * g], inv_s, b.x)),
-                                             tanh_fast(fmaf(acc[rt][c][4 * g + 1], inv_s, b.y)),
-                                             tanh_fast(fmaf(acc[rt][c][4 * g + 2], inv_s, b.z)),
-                                             tanh_fast(fmaf(acc[rt][c][4 * g + 3], inv_s, b.w)));
-                if (i < MU && row0 + i < R) *reinterpret_cast<float4*>(e2 + (row0 + i) * H + n0) = y;
+                const float4 y = tanh_bias4(acc[rt][c], g, inv_s, lds4(bias + n0));
+                if (i < MU && row0 + i < R) st4g(e2 + (row0 + i) * H + n0, y);
                 *reinterpret_cast<float4*>(Y + i * LDY + n0) = y;
             }
     }
     __syncthreads();
+    // (float4-wide and from the agent's first row: its own form of qs_policy.h agent_sum, see attn_pool_x3_kernel)
     const float inv = 1.f / (float)K;
     constexpr int H4 = H / 4;
     for (int e = tid; e < AB * H4; e += NTHR) {
@@ -235,11 +229,8 @@ __device__ __forceinline__ void embed_e2_epilogue(const f32x16 (&acc)[RT][Geo<H>
         const long agent = row0 / K + a;
         if (agent < B) {
             float4 s = lds4(Y + (a * K) * LDY + 4 * c4);
-            for (int k = 1; k < K; ++k) {
-                const float4 v = lds4(Y + (a * K + k) * LDY + 4 * c4);
-                s = make_float4(s.x + v.x, s.y + v.y, s.z + v.z, s.w + v.w);
-            }
-            *reinterpret_cast<float4*>(e_mean + agent * H + 4 * c4) = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
+            for (int k = 1; k < K; ++k) s = f4_add(s, lds4(Y + (a * K + k) * LDY + 4 * c4));
+            st4g(e_mean + agent * H + 4 * c4, make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv));
         }
     }
 }
@@ -253,20 +244,26 @@ constexpr size_t pool_x3_lds_bytes() {
     return (size_t)(2 * MROWS * GeoX3<H>::LDH) * 2 + (size_t)(3 * MROWS + 4 * H + NWAVE * MROWS) * 4;
 }
 
-// attn_embed_kernel with the split-f16 contraction (same inputs, same outputs: e2 rows and means in fp32)
-template <int H>
-__global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_embed_x3_kernel(const float* __restrict__ obs, int stride, int so,
-                                                               int off, int B, int K, int nd, Towers tw) {
+// attn_embed_kernel with the split-f16 contraction (same inputs, same outputs: e2 rows and means in fp32): the one
+// embedding forward of the rollout (attn_embed_x3_kernel) and of the PPO update (attn_embed_train_x3_kernel,
+// qs_policy_train.h).  TRAIN: e1 is saved to HBM for the backward, and layer 2's first weights are fetched ahead of
+// those stores (WQueue); the rollout, with no stores in the way, fetches them at the layer.
+template <int H, bool TRAIN>
+__device__ __forceinline__ void attn_embed_x3_body(const float* __restrict__ obs, int stride, int so, int off, int B,
+                                                   int K, int nd, const qs_attn_tower& t, float* __restrict__ e1) {
     constexpr int LDH = GeoX3<H>::LDH, LD0 = GeoX3<KD0>::LDH, CT = Geo<H>::CT;
     extern __shared__ float4 smem4[];
     _Float16* xh = reinterpret_cast<_Float16*>(smem4);
     const TileX3 X{xh, xh + MROWS * LDH, LDH};
     const TileX3 X0{xh + 2 * MROWS * LDH, xh + 2 * MROWS * LDH + MROWS * LD0, LD0};
     float* BI = reinterpret_cast<float*>(xh + 2 * MROWS * LDH + 2 * MROWS * LD0);   // b_e1, b_e2
-    const qs_attn_tower& t = tw.t[blockIdx.y];
+    const uint4* we2 = reinterpret_cast<const uint4*>(t.w_e2p);
     const int AB = MROWS / K, MU = AB * K;
     const long R = (long)B * K, row0 = (long)blockIdx.x * MU;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    QS_STAMP_DECL
+    QS_RTSTAMP(12);
+    QS_STAMP(0);
     for (int n = tid; n < H; n += NTHR) {
         BI[n] = t.b_e1[n];
         BI[H + n] = t.b_e2[n];
@@ -275,17 +272,38 @@ __global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2)))
     // agent j % B (the reference's row pairing)
     gather_rows0(obs, stride, so, off, B, K, nd, row0, MU, R, tid, [&](int r, int c, float v) { X0.put(r, c, X3_SIN * v); });
     __syncthreads();
+    QS_STAMP(1);
     f32x16 acc[RT][CT];
     mfma_layer_x3<H, KD0, true, false>(X0, reinterpret_cast<const uint4*>(t.w_e1p), acc, wave, lane);
-    store_tanh_x3<H>(X, acc, 1.f / (X3_SIN * X3_SW), wave, lane, [&](int i, int n0) {
-        return (i < MU && row0 + i < R) ? lds4(BI + n0) : make_float4(0.f, 0.f, 0.f, 0.f);
-    });
+    QS_STAMP(2);
+    WQueue<H> qe2;
+    if constexpr (TRAIN) qe2 = mfma_prefetch_x3<H>(we2, wave, lane);   // ahead of e1's stores
+    store_tanh_x3<H>(X, acc, 1.f / (X3_SIN * X3_SW), wave, lane,
+                     [&](int i, int n0) {
+                         return (i < MU && row0 + i < R) ? lds4(BI + n0) : make_float4(0.f, 0.f, 0.f, 0.f);
+                     },
+                     [&](int i, int n0, float4 y) {
+                         if constexpr (TRAIN)
+                             if (i < MU && row0 + i < R) st4g(e1 + (row0 + i) * H + n0, y);
+                     });
     __syncthreads();
-    mfma_layer_x3<H, H, true, true>(X, reinterpret_cast<const uint4*>(t.w_e2p), acc, wave, lane);   // PIN: its scheduling fences
+    QS_STAMP(3);
+    if constexpr (!TRAIN) qe2 = mfma_prefetch_x3<H>(we2, wave, lane);
+    mfma_layer_x3<H, H, true, true>(X, we2, acc, wave, lane, qe2);   // PIN: its scheduling fences
     __syncthreads();   // every wave has read the tile
+    QS_STAMP(4);
     // e2 to HBM straight from the epilogue (fp32 tanh values) and into an fp32 tile over the split tile's bytes
     // (the last layer: the split tile is not read again), whose rows the per-agent means then read as float4
     embed_e2_epilogue<H>(acc, BI + H, t.e2, t.e_mean, smem4, row0, MU, R, B, K, AB, wave, lane, tid);
+    QS_STAMP(5);
+    QS_STAMP(6);
+    QS_RTSTAMP(13);
+    if (blockIdx.y == 0) QS_STAMP_FLUSH();
+}
+template <int H>
+__global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_embed_x3_kernel(
+    const float* __restrict__ obs, int stride, int so, int off, int B, int K, int nd, Towers tw) {
+    attn_embed_x3_body<H, false>(obs, stride, so, off, B, K, nd, tw.t[blockIdx.y], nullptr);
 }
 
 // the block's e2 rows (fp32, HBM) into the split tile (zero rows past the data)
@@ -300,7 +318,7 @@ __device__ __forceinline__ void load_rows_x3(const TileX3& X, const float* __res
         const long j = row0 + r;
         const bool ok = r < MU && j < R;
         const float okf = ok ? 1.f : 0.f;
-        v[u] = reinterpret_cast<const float4*>(src + (ok ? j : 0) * H)[c4];   // unconditional (see the P loads)
+        v[u] = reinterpret_cast<const float4*>(src + (ok ? j : 0) * H)[c4];   // unconditional (see acc_from_P)
         v[u] = make_float4(v[u].x * okf, v[u].y * okf, v[u].z * okf, v[u].w * okf);
     }
 #pragma unroll
@@ -310,7 +328,10 @@ __device__ __forceinline__ void load_rows_x3(const TileX3& X, const float* __res
     }
 }
 
-// attn_pool_kernel with the split-f16 contraction
+// attn_pool_kernel with the split-f16 contraction.  The rollout's dominant kernel, at 252 of 256 VGPRs (H = 256): its
+// P start, softmax and final sum stay written out here.  On the shared forms (acc_from_P, score_softmax, agent_sum:
+// same operations) it kept 252 VGPRs and no spill but compiled to another schedule and measured 1.2 % slower; a body
+// shared with attn_pool_train_x3_kernel spilled ("layout of the sources").
 template <int H>
 __global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_pool_x3_kernel(int B, int K, Towers tw) {
     constexpr int LDH = GeoX3<H>::LDH, CT = Geo<H>::CT;
@@ -325,16 +346,11 @@ __global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const long R = (long)B * K, row0 = (long)blockIdx.x * MU;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     constexpr float SS = X3_SX * X3_SW, iSS = 1.f / SS;
-    for (int n = tid; n < H; n += NTHR) {
-        A3[n] = t.w_a3[n];
-        A3[H + n] = t.b_a2[n];
-        A3[2 * H + n] = t.b_v1[n];
-        A3[3 * H + n] = t.b_v2[n];
-    }
+    load_a3_table<H>(A3, t, tid);
     // attention_mlp: a1 = tanh(e2 A_e^T + P[j % B]): the accumulators start at P (scaled like the products)
     f32x16 acc[RT][CT];
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
+    for (int rt = 0; rt < RT; ++rt) {   // acc_from_P, written out
         const int i = acc_i(rt, lane);
         const int j = (int)row0 + i;
         const bool ok = i < MU && j < R;
@@ -344,9 +360,6 @@ __global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2)))
         for (int c = 0; c < CT; ++c)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                // loaded unconditionally (row 0 stands in for an unused row) and zeroed by a product: a
-                // conditional load (or a select the compiler sinks back into a branch) costs a branch + a full
-                // wait per load, 16 serial HBM latencies
                 float4 v = *reinterpret_cast<const float4*>(pr + acc_n0<H>(wave, c, g, lane));
                 v = make_float4(v.x * okf, v.y * okf, v.z * okf, v.w * okf);
                 acc[rt][c][4 * g] = SS * v.x; acc[rt][c][4 * g + 1] = SS * v.y;
@@ -370,7 +383,7 @@ __global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2)))
     __syncthreads();
     if (tid < MROWS) SC[tid] = ((SCP[tid] + SCP[MROWS + tid]) + (SCP[2 * MROWS + tid] + SCP[3 * MROWS + tid])) + t.b_a3;
     __syncthreads();
-    if (tid < AB) {   // softmax over the agent's K rows
+    if (tid < AB) {   // score_softmax, written out
         const int base = tid * K;
         float m = SC[base];
         for (int k = 1; k < K; ++k) m = fmaxf(m, SC[base + k]);
@@ -399,16 +412,12 @@ __global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int n0 = acc_n0<H>(wave, c, g, lane);
-                const float4 b = lds4(A3 + 3 * H + n0);
-                *reinterpret_cast<float4*>(Y + i * LDY + n0) =
-                    make_float4(wi * tanh_fast(fmaf(acc[rt][c][4 * g], iSS, b.x)),
-                                wi * tanh_fast(fmaf(acc[rt][c][4 * g + 1], iSS, b.y)),
-                                wi * tanh_fast(fmaf(acc[rt][c][4 * g + 2], iSS, b.z)),
-                                wi * tanh_fast(fmaf(acc[rt][c][4 * g + 3], iSS, b.w)));
+                const float4 h = tanh_bias4(acc[rt][c], g, iSS, lds4(A3 + 3 * H + n0));
+                *reinterpret_cast<float4*>(Y + i * LDY + n0) = f4_scale(h, wi);
             }
     }
     __syncthreads();
-    for (int e = tid; e < AB * (H / 4); e += NTHR) {   // the agent's weighted rows summed in k order, float4 wide
+    for (int e = tid; e < AB * (H / 4); e += NTHR) {   // agent_sum, float4 wide
         const int a = e / (H / 4), c4 = e - a * (H / 4);
         const long agent = row0 / K + a;
         if (agent < B) {
@@ -418,12 +427,6 @@ __global__ __launch_bounds__(NTHR, 2) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
     }
 }
-
-}  // namespace pol
-}  // namespace qs
-
-namespace qs {
-namespace pol {
 
 // ------------------------------------------------------------------------------------------------------------------
 // The encoder's feed_forward (quad_multi_model.py:250-353 QuadMultiEncoder: Linear(2R -> 2R) + Tanh on the
