@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define QS_ABI_VERSION 15
+#define QS_ABI_VERSION 16
 #define QS_MAX_AGENTS 128           /* drones per env: up to 64 inside one 64-lane wavefront, 128 = a two-wave
                                        workgroup per env (flavor B without obstacles; paper/fps_compare.py:7) */
 #define QS_MAX_DR_CHOICES 8         /* entries per obstacle domain-randomisation list */
@@ -77,8 +77,12 @@ enum qs_neighbor_obs {              /* quad_utils.py:40-58 (QUADS_NEIGHBOR_OBS_T
     QS_NEIGHBOR_NDIST_NSANGLE = 4,     /* 3, flavor A, camera model */
     QS_NEIGHBOR_DIST_ANGLE_HEADING = 5,    /* 3, flavor A */
     QS_NEIGHBOR_DIST_SANGLE_SHEADING = 6,  /* 5, flavor A */
-    QS_NEIGHBOR_POS = 7,               /* 3, flavor A */
-    QS_NEIGHBOR_NPOS = 8,              /* 3, flavor A (the reference discards its noise) */
+    QS_NEIGHBOR_POS = 7,               /* 3, both flavors */
+    QS_NEIGHBOR_NPOS = 8,              /* 3, both flavors (the reference discards its noise) */
+    QS_NEIGHBOR_POS_VEL_R = 9,         /* 15, flavor B: rel pos, rel vel, rot[i]^T rot[j] row-major */
+    QS_NEIGHBOR_POS_RZ = 10,           /* 6, flavor B: rel pos, rot[i]^T rot[j][:, 2] */
+    QS_NEIGHBOR_POS_VEL_RZ = 11,       /* 9, flavor B: rel pos, rel vel, that Rz vector */
+    QS_NEIGHBOR_RNG3 = 12,             /* 3, flavor B: uniform [0, 1) noise, no geometry */
 };
 
 enum qs_scenario {
@@ -244,7 +248,7 @@ enum qs_rinfo {
     QS_RI_GOAL_DIST = 0             /* flavor A */
 };
 enum qs_env_flags {
-    QS_EF_STALE = 1,                /* stale_vel / QS_F_HEADING hold QuadrotorEnvMulti.vel / .heading */
+    QS_EF_STALE = 1,                /* stale_vel (and its rot rows) / QS_F_HEADING hold QuadrotorEnvMulti.vel (.rot) / .heading */
     QS_EF_SUCCESS = 2,              /* flavor A episode_success (a capture happened this episode)     */
     QS_EF_HAS_POS = 4,              /* drones have been placed once (dynamic_repulsive.py:38 hasattr) */
     /* written by every flavor-B step, read by the replay kernel: */
@@ -282,7 +286,9 @@ typedef struct qs_buffers {         /* device pointers (valid for the handle's l
     float* env_f;                   /* [QS_NENVF, E] */
     float* obst;                    /* [E, M, 2] pillar xy (MultiObstacles.pos_arr order); M = num_obstacles, or
                                        the largest dr_counts entry (an env uses its first QS_E_OBST_M slots) */
-    float* stale_vel;               /* [3, I]  QuadrotorEnvMulti.vel as last seen by a reset */
+    float* stale_vel;               /* [3, I]  QuadrotorEnvMulti.vel as last seen by a reset; the neighbour types
+                                       with an R / Rz part append [9, I]: QuadrotorEnvMulti.rot likewise,
+                                       row-major (the identity before the first step) */
     float* obs;                     /* [I, obs_dim] */
     float* term_obs;                /* [I, obs_dim] rows of envs that finished this step */
     float* rew;                     /* [I] */
@@ -424,7 +430,7 @@ typedef struct qs_replay_buffers {  /* device pointers, valid while replay is en
     int32_t* perm;                  /* [buffer_size, E] deque position -> slot (positions >= BUF_N: free) */
     int32_t* nrep;                  /* [buffer_size, E] num_replayed per slot                          */
     uint32_t* store;                /* [E, keep + buffer_size, snap_words]: ring slots, then buffer slots */
-    size_t snap_words;              /* words per snapshot: per drone (QS_NF + QS_NI + 3 + obs_dim) fields
+    size_t snap_words;              /* words per snapshot: per drone (QS_NF + QS_NI + 3 [+ 9 stale rot] + obs_dim) fields
                                        drone-minor, then env ints QS_NE, env floats QS_NENVF, obstacle xy
                                        2M, obs rows N x obs_dim */
 } qs_replay_buffers;

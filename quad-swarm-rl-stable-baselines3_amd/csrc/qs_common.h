@@ -12,12 +12,18 @@
 
 namespace qs {
 
-// flavor-A neighbour features (get_rel_pos_vel_item, quadrotor_multi_rewards.py:326-420), in the
-// reference's concatenation order
+// neighbour features (get_rel_pos_vel_item: flavor A quadrotor_multi_rewards.py:326-420, flavor B
+// quadrotor_multi.py:275-319), in the reference's concatenation order.  Flavor B: POS / NPOS, VEL, then R or RZ
+// (rot[i]^T rot[j], or its third column); RNG (rng3) stands alone.
 enum : int {
     QS_NF_DIST = 1, QS_NF_NDIST = 2, QS_NF_ANGLE = 4, QS_NF_SANGLE = 8, QS_NF_NSANGLE = 16,
-    QS_NF_HEADING = 32, QS_NF_SHEADING = 64, QS_NF_NPOS = 128, QS_NF_POS = 256, QS_NF_VEL = 512
+    QS_NF_HEADING = 32, QS_NF_SHEADING = 64, QS_NF_NPOS = 128, QS_NF_POS = 256, QS_NF_VEL = 512,
+    QS_NF_R = 1024, QS_NF_RZ = 2048, QS_NF_RNG = 4096
 };
+// float4 entries per drone slot that a flavor-B feature set adds to the exchange tile (the neighbour's rotation rows,
+// or its third column), and the rows of the stale buffer (vel, then the 9 rot entries for the same types)
+constexpr int xch_rot_f4(int nfeat) { return (nfeat & QS_NF_R) ? 3 : ((nfeat & QS_NF_RZ) ? 1 : 0); }
+constexpr int stale_rows(int nfeat) { return (nfeat & (QS_NF_R | QS_NF_RZ)) ? 12 : 3; }
 
 struct KP {
     int E, N, I, obs_dim, so_dim, K, neighbor, obs_repr, ep_len, sim_steps, svd_every, sense, downwash, collide;
@@ -164,7 +170,8 @@ constexpr Geo reset_geo(int npad) { return geo_of(npad, 1); }
 
 // Dynamic LDS of a launch, as word (4-byte) offsets:
 //   obs    [slots, obs_dim]   the observation tile (free as scratch until the obs phase of a step)
-//   xch    [slots] x 2 float4 the neighbour exchange tile
+//   xch    [slots] x 2 float4 the neighbour exchange tile, then [slots] x xrot float4: the drones' rotation rows
+//                             (xrot = 3) or third rotation column (1) for the flavor-B types that read them (else 0)
 //   scr    64 words           env collectives / flags (QS_B_SCR_* / QS_A_SCR_* below)
 //   otile  [epb, M] float2    obstacle kernels: the envs' pillar lists
 //   oscr   [epb]              obstacle kernels: QS_OBST_SCRATCH bytes of reset scratch per env (ObstScratch)
@@ -178,13 +185,14 @@ constexpr bool scen_tables(bool obst, int scen_b) { return obst ? scen_b >= SC_O
 // The map of a launch of geometry g (g.SLOTS drone rows, g.EPB envs per workgroup); obst: an obstacle kernel with
 // M pillar slots per env.
 struct LdsMap {
-    int obs, xch, scr, otile, oscr, tab;
+    int obs, xch, xrot, scr, otile, oscr, tab;
 };
-constexpr LdsMap lds_map(Geo g, int obs_dim, int M, bool obst) {
+constexpr LdsMap lds_map(Geo g, int obs_dim, int M, bool obst, int xrot = 0) {
     LdsMap m{};
     m.obs = 0;
     m.xch = g.SLOTS * obs_dim;
-    m.scr = m.xch + g.SLOTS * 8;
+    m.xrot = m.xch + g.SLOTS * 8;
+    m.scr = m.xrot + g.SLOTS * 4 * xrot;
     m.otile = m.scr + 64;
     m.oscr = m.otile + (obst ? g.EPB * 2 * M : 0);
     m.tab = m.oscr + (obst ? g.EPB * (QS_OBST_SCRATCH / 4) : 0);

@@ -116,18 +116,88 @@ __device__ __forceinline__ void xch_put(float4* xch, int lane, const float* P, c
     xch[2 * lane] = make_float4(P[0], P[1], P[2], 0.f);
     xch[2 * lane + 1] = make_float4(V[0], V[1], V[2], 0.f);
 }
+// the rotation part of the tile (LdsMap::xrot) for the types with an R part (the 3 rows of R) or an Rz part (its
+// third column); R row-major
+__device__ __forceinline__ void xch_put_rot(const KP& kp, float4* xrot, int lane, const float* R) {
+    if (kp.nfeat & QS_NF_R) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) xrot[3 * lane + c] = make_float4(R[3 * c], R[3 * c + 1], R[3 * c + 2], 0.f);
+    } else if (kp.nfeat & QS_NF_RZ) {
+        xrot[lane] = make_float4(R[2], R[5], R[8], 0.f);
+    }
+}
 
-// pos_vel neighbour obs: neighborhood_indices (quadrotor_multi.py:344-375) + extend_obs_space
-// clip (:328-342).  Key = |[rel_pos, rel_vel]| clamped at 0.01 (compared squared, clamp 1e-4);
-// stable (index) tie-break like numpy's insertion sort; k == N-1 keeps index order (all keys 0).
+// One neighbour's slot (get_rel_pos_vel_item quadrotor_multi.py:275-319 + the extend_obs_space clip
+// quadrotor_single.py:280-326): rel pos (rxyz box), rel vel (rvxyz box), then R_i^T R_j row-major or its third
+// column R_i^T R_j[:, 2] (+-1).  r = the 6 relative components, j = the neighbour's tile slot, R = the observer's
+// rotation.  PAIRS: the slot is 8-byte aligned and 6 floats wide.
+template <bool PAIRS>
+__device__ __forceinline__ void nbr_slot(const KP& kp, int m, const float4* xrot, int j, const float* r, const float* R, float* o) {
+    const float vm = 2.f * kp.vxyz_max;
+    const float o0 = clampf(r[0], -kp.room_range[0], kp.room_range[0]);
+    const float o1 = clampf(r[1], -kp.room_range[1], kp.room_range[1]);
+    const float o2 = clampf(r[2], -kp.room_range[2], kp.room_range[2]);
+    if (!(m & QS_NF_VEL)) {
+        o[0] = o0; o[1] = o1; o[2] = o2;
+        o += 3;
+    } else {
+        const float o3 = clampf(r[3], -vm, vm), o4 = clampf(r[4], -vm, vm), o5 = clampf(r[5], -vm, vm);
+        if (PAIRS) {
+            float2* o2p = reinterpret_cast<float2*>(o);
+            o2p[0] = make_float2(o0, o1);
+            o2p[1] = make_float2(o2, o3);
+            o2p[2] = make_float2(o4, o5);
+        } else {
+            o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3; o[4] = o4; o[5] = o5;
+        }
+        o += 6;
+    }
+    if (m & QS_NF_R) {
+        const float4 r0 = xrot[3 * j], r1 = xrot[3 * j + 1], r2 = xrot[3 * j + 2];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {   // row a of R_i^T R_j = column a of R_i against the rows of R_j
+            o[3 * a] = clampf(R[a] * r0.x + R[3 + a] * r1.x + R[6 + a] * r2.x, -1.f, 1.f);
+            o[3 * a + 1] = clampf(R[a] * r0.y + R[3 + a] * r1.y + R[6 + a] * r2.y, -1.f, 1.f);
+            o[3 * a + 2] = clampf(R[a] * r0.z + R[3 + a] * r1.z + R[6 + a] * r2.z, -1.f, 1.f);
+        }
+    } else if (m & QS_NF_RZ) {
+        const float4 z = xrot[j];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) o[a] = clampf(R[a] * z.x + R[3 + a] * z.y + R[6 + a] * z.z, -1.f, 1.f);
+    }
+}
+
+// Neighbour obs: neighborhood_indices (quadrotor_multi.py:344-375) + extend_obs_space clip (:328-342).
+// PV: the type is pos_vel (its feature set and slot width are constants of the instantiation); else
+// the feature set kp.nfeat: pos / npos, pos_vel_R, pos_Rz, pos_vel_Rz, rng3.
+// Key = the norm of the whole packed row clamped at 0.01.  It is compared squared and without the constant the R
+// block (3) or the Rz block (1) adds, which keeps the resolution of near neighbours; with that constant the clamp
+// never binds, without an R part it is 1e-4 on the squared key.  Stable (index) tie-break like numpy's insertion
+// sort; k == N-1 keeps index order (all keys 0).  rng3 (np.random.rand(3) per slot, drawn apart from the values
+// the reference sorts by) is pure noise: stream `rstream`, block = slot, no selection.
 // Reads the exchange tile (caller has synchronised).  With Q sub-lanes per drone, sub-lane q owns
 // the candidates j = q + Q t: it builds their keys, gathers the other sub-lanes' keys by DPP, ranks
 // its own candidates and writes those that land among the K nearest.  Only write == true stores.
-template <int NPAD, int Q>
-__device__ __forceinline__ void neighbor_obs(const KP& kp, const float4* xch, int dbase, int di, int q, const float* P, const float* V,
-                             bool write, float* out) {
+template <int NPAD, int Q, bool PV>
+__device__ __forceinline__ void neighbor_obs_t(const KP& kp, const float4* xch, const float4* xrot, int dbase, int di, int q,
+                                               const float* P, const float* V, const float* R, const Rng& rng, uint32_t gid,
+                                               uint32_t rstream, bool write, float* out) {
     constexpr int PJ = (NPAD + Q - 1) / Q;   // candidates per sub-lane
     constexpr bool KEEP = PJ <= 8;           // keep the relative vectors in VGPRs between passes
+    const int nf = PV ? (QS_NF_POS | QS_NF_VEL) : kp.nfeat;
+    const int W = PV ? 6 : kp.nfd;           // floats per slot
+    if (!PV && (nf & QS_NF_RNG)) {
+        if (write && q == 0)
+            for (int r = 0; r < kp.K; ++r) {
+                float u[4];
+                uniforms4(rng, gid, rstream, (uint32_t)r, u);
+                float* o = out + kp.so_dim + r * 3;
+                o[0] = u[0]; o[1] = u[1]; o[2] = u[2];
+            }
+        return;
+    }
+    const bool hasv = (nf & QS_NF_VEL) != 0;
+    const float kmin = (nf & (QS_NF_R | QS_NF_RZ)) ? 0.f : 1e-4f;
     float key[PJ];
     float rel[KEEP ? PJ : 1][6];
     const bool sorted = kp.K < kp.N - 1;
@@ -137,9 +207,11 @@ __device__ __forceinline__ void neighbor_obs(const KP& kp, const float4* xch, in
         const int jj = j < NPAD ? j : NPAD - 1;
         const float4 pj = xch[2 * (dbase + jj)], vj = xch[2 * (dbase + jj) + 1];
         const float r[6] = {pj.x - P[0], pj.y - P[1], pj.z - P[2], vj.x - V[0], vj.y - V[1], vj.z - V[2]};
-        const float s = r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3] + r[4] * r[4] + r[5] * r[5];
+        float s;
+        if (PV || hasv) s = r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3] + r[4] * r[4] + r[5] * r[5];
+        else s = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
         const bool valid = (j != di) && (j < kp.N);
-        key[t] = valid ? (sorted ? fmaxf(s, 1e-4f) : 0.f) : __builtin_inff();
+        key[t] = valid ? (sorted ? fmaxf(s, PV ? 1e-4f : kmin) : 0.f) : __builtin_inff();
         if (KEEP) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) rel[KEEP ? t : 0][c] = r[c];
@@ -161,8 +233,8 @@ __device__ __forceinline__ void neighbor_obs(const KP& kp, const float4* xch, in
         }
     }
     if (!write) return;
-    const float vm = 2.f * kp.vxyz_max;
-    const bool pairs = ((kp.so_dim | kp.obs_dim) & 1) == 0;   // 8-byte aligned slots: ds_write_b64
+    // 8-byte aligned slots: ds_write_b64 (pos_vel alone: the other widths go out as single words)
+    const bool pairs = PV && ((kp.so_dim | kp.obs_dim) & 1) == 0;
     if constexpr (NPAD >= 64) {
         // 128-drone envs and the sub-lane (multi-wave) envs always take this path (k = N - 1 keys are all 0: the
         // passes pick index order, as the ranking does); their ranking is not compiled
@@ -193,13 +265,8 @@ __device__ __forceinline__ void neighbor_obs(const KP& kp, const float4* xch, in
                 pjx = bj;
                 if (Q > 1 && q != 0) continue;   // the pair's first sub-lane writes the slot
                 const float4 pj = xch[2 * (dbase + bj)], vj = xch[2 * (dbase + bj) + 1];
-                const float o0 = clampf(pj.x - P[0], -kp.room_range[0], kp.room_range[0]);
-                const float o1 = clampf(pj.y - P[1], -kp.room_range[1], kp.room_range[1]);
-                const float o2 = clampf(pj.z - P[2], -kp.room_range[2], kp.room_range[2]);
-                const float o3 = clampf(vj.x - V[0], -vm, vm), o4 = clampf(vj.y - V[1], -vm, vm);
-                const float o5 = clampf(vj.z - V[2], -vm, vm);
-                float* o = out + kp.so_dim + r * 6;
-                o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3; o[4] = o4; o[5] = o5;
+                const float rr[6] = {pj.x - P[0], pj.y - P[1], pj.z - P[2], vj.x - V[0], vj.y - V[1], vj.z - V[2]};
+                nbr_slot<false>(kp, nf, xrot, dbase + bj, rr, R, out + kp.so_dim + r * W);
             }
             return;
         }
@@ -221,22 +288,20 @@ __device__ __forceinline__ void neighbor_obs(const KP& kp, const float4* xch, in
                 r[0] = pj.x - P[0]; r[1] = pj.y - P[1]; r[2] = pj.z - P[2];
                 r[3] = vj.x - V[0]; r[4] = vj.y - V[1]; r[5] = vj.z - V[2];
             }
-            const float o0 = clampf(r[0], -kp.room_range[0], kp.room_range[0]);
-            const float o1 = clampf(r[1], -kp.room_range[1], kp.room_range[1]);
-            const float o2 = clampf(r[2], -kp.room_range[2], kp.room_range[2]);
-            const float o3 = clampf(r[3], -vm, vm), o4 = clampf(r[4], -vm, vm), o5 = clampf(r[5], -vm, vm);
-            float* o = out + kp.so_dim + rank * 6;
-            if (pairs) {
-                float2* o2p = reinterpret_cast<float2*>(o);
-                o2p[0] = make_float2(o0, o1);
-                o2p[1] = make_float2(o2, o3);
-                o2p[2] = make_float2(o4, o5);
-            } else {
-                o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3; o[4] = o4; o[5] = o5;
-            }
+            float* o = out + kp.so_dim + rank * W;
+            if (pairs) nbr_slot<true>(kp, nf, xrot, dbase + j, r, R, o);
+            else nbr_slot<false>(kp, nf, xrot, dbase + j, r, R, o);
         }
     }
     }
+}
+// the type's instantiation: pos_vel apart, so that its code is what the 6-float form compiled to
+template <int NPAD, int Q>
+__device__ __forceinline__ void neighbor_obs(const KP& kp, const float4* xch, const float4* xrot, int dbase, int di, int q,
+                                             const float* P, const float* V, const float* R, const Rng& rng, uint32_t gid,
+                                             uint32_t rstream, bool write, float* out) {
+    if (kp.neighbor == QS_NEIGHBOR_POS_VEL) neighbor_obs_t<NPAD, Q, true>(kp, xch, xrot, dbase, di, q, P, V, R, rng, gid, rstream, write, out);
+    else neighbor_obs_t<NPAD, Q, false>(kp, xch, xrot, dbase, di, q, P, V, R, rng, gid, rstream, write, out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -876,9 +941,10 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
     const int dbase = el * NPAD;          // first drone slot of the env
     const int nenv_blk = min(EPB, kp.E - env0);
     const int rows = nenv_blk * kp.N;
-    auto L = [&] { return lds_map(G::geo(), kp.obs_dim, kp.M, OBST); };   // the LDS map, evaluated where a pointer is taken
+    auto L = [&] { return lds_map(G::geo(), kp.obs_dim, kp.M, OBST, xch_rot_f4(kp.nfeat)); };   // the LDS map, evaluated where a pointer is taken
     float* row = lds + L().obs + (size_t)(el * kp.N + di) * kp.obs_dim;
     float4* xch = reinterpret_cast<float4*>(lds + L().xch);
+    float4* xrot = reinterpret_cast<float4*>(lds + L().xrot);   // the tile's rotation part (R / Rz neighbour types)
     const uint64_t lmask = (LPE >= 64) ? ~0ull : ((1ull << LPE) - 1ull);
     // env-level collectives; WIDE: their LDS slots and the env counters' exchange in the scratch words
     uint64_t* wscr = reinterpret_cast<uint64_t*>(lds + L().scr);
@@ -1044,7 +1110,10 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
     // ---- swarm phase: collisions + proximity (quadrotor_multi.py:537-568, 608-622) ----
     Row cur{};
     float pen = 0.f;
-    if (q == 0) xch_put(xch, dbase + di, d.pos, d.vel);
+    if (q == 0) {   // (the rotation is final here: the interactions below change velocities only)
+        xch_put(xch, dbase + di, d.pos, d.vel);
+        xch_put_rot(kp, xrot, dbase + di, d.rot);
+    }
     lds_sync();
     if (kp.N > 1) {
         // sub-lane q tests the partners j = q + Q t (LDS reads issued back to back, branch-free
@@ -1410,7 +1479,7 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
     QS_STAMP(4);
     if (SCEN_STEP) QS_PRIO_DROP(23);   // goal-scenario kernels: c3mix 9.38 -> 9.30 us (C3 neutral-to-worse: kept)
     // ---- observations (post-impulse state; quadrotor_multi.py:704-720) ----
-    const bool nbr = kp.neighbor == QS_NEIGHBOR_POS_VEL && kp.K > 0;
+    const bool nbr = kp.neighbor != QS_NEIGHBOR_NONE && kp.K > 0;
     if (nbr && ec.wany(vchanged)) {  // impulses changed velocities: refresh the tile
         lds_sync();
         if (q == 0) xch_put(xch, dbase + di, d.pos, d.vel);
@@ -1423,7 +1492,7 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
         self_obs_z(kp, dv, zs, rng, gid, S_SENSOR, row);
     }
     QS_STAMP(6);
-    if (nbr) neighbor_obs<NPAD, Q>(kp, xch, dbase, di, q, d.pos, d.vel, active, row);
+    if (nbr) neighbor_obs<NPAD, Q>(kp, xch, xrot, dbase, di, q, d.pos, d.vel, d.rot, rng, gid, S_NBR_RNG, active, row);
     if (OBST && active) sdf_obs_q<Q>(kp, og, myob, d.pos[0], d.pos[1], row + kp.obs_dim - 9, q);   // MultiObstacles.step
     QS_STAMP(7);
     // non-finite guard of the stepped drone and its reward (before a fused reset replaces the drone)
@@ -1492,6 +1561,9 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
             }
         }
         float sv[3] = {d.vel[0], d.vel[1], d.vel[2]};  // QuadrotorEnvMulti.vel seen by the reset (:477)
+        float sr[9];                                   // and QuadrotorEnvMulti.rot (the types with an R / Rz part)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) sr[k] = d.rot[k];
         if (OBST) {   // new obstacle map + scenario per finished env (one lane each)
             if (active && done && di == 0 && q == 0) {
                 oscr[el].mi = omi;
@@ -1523,6 +1595,10 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
                 b.stale[0 * kp.I + g] = sv[0];
                 b.stale[1 * kp.I + g] = sv[1];
                 b.stale[2 * kp.I + g] = sv[2];
+                if (xch_rot_f4(kp.nfeat)) {
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) b.stale[(size_t)(3 + k) * kp.I + g] = sr[k];
+                }
             }
             float spawn[3] = {kp.goal[0], kp.goal[1], kp.goal[2]}, goal[3] = {kp.goal[0], kp.goal[1], kp.goal[2]};
             if (OBST) obstacle_spawn_goal(kp, oscr + el, di, rng, gid, spawn, goal, OSCEN ? stab : nullptr);
@@ -1545,9 +1621,10 @@ __global__ __launch_bounds__(StepGeo<NPAD>::WGS) void step_kernel(const KP* __re
             store_drone_q<Q, false, NIW>(kp, b, g, q, active && done, d);
         }
         if (nbr) {
+            // (the tile's rotation part still holds the stepped rotations: what the reset observes)
             if (q == 0) xch_put(xch, dbase + di, d.pos, sv);
             lds_sync();
-            neighbor_obs<NPAD, Q>(kp, xch, dbase, di, q, d.pos, sv, active && done, row);
+            neighbor_obs<NPAD, Q>(kp, xch, xrot, dbase, di, q, d.pos, sv, sr, rng, gid, S_NBR_RNG_RESET, active && done, row);
         }
         if (OBST && lead && done) {
             sdf_obs(kp, og, myob, d.pos[0], d.pos[1], row + kp.obs_dim - 9);   // MultiObstacles.reset
@@ -1611,7 +1688,7 @@ __global__ __launch_bounds__(reset_geo(NPAD).WGS) void reset_kernel(const KP* __
     constexpr Geo G = reset_geo(NPAD);   // one lane per drone
     constexpr int WGS = G.WGS, EPB = G.EPB, SLOTS = G.SLOTS;
     constexpr bool WIDE = NPAD > 64;
-    auto L = [&] { return lds_map(G, kp.obs_dim, kp.M, OBST); };   // the LDS map, evaluated where a pointer is taken
+    auto L = [&] { return lds_map(G, kp.obs_dim, kp.M, OBST, xch_rot_f4(kp.nfeat)); };   // the LDS map, evaluated where a pointer is taken
     const int lane = threadIdx.x;
     const int el = lane / NPAD, di = lane % NPAD;
     const int env0 = blockIdx.x * EPB;
@@ -1631,6 +1708,11 @@ __global__ __launch_bounds__(reset_geo(NPAD).WGS) void reset_kernel(const KP* __
     float sv[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) sv[c] = stale_valid ? b.stale[c * kp.I + g] : d.vel[c];
+    // stale QuadrotorEnvMulti.rot likewise (the types with an R / Rz part keep it after the vel rows)
+    const bool srot = xch_rot_f4(kp.nfeat) != 0;
+    float sr[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) sr[c] = (srot && stale_valid) ? b.stale[(size_t)(3 + c) * kp.I + g] : d.rot[c];
     float2* otile = reinterpret_cast<float2*>(lds + L().otile);
     ObstScratch* oscr = reinterpret_cast<ObstScratch*>(lds + L().oscr);
     float* stab = lds + L().tab + el * scen_stride(NPAD);
@@ -1669,11 +1751,13 @@ __global__ __launch_bounds__(reset_geo(NPAD).WGS) void reset_kernel(const KP* __
         reset_drone(kp, d, rng, kp.id0 + (uint32_t)g, spawn, goal);
         self_obs(kp, d, rng, kp.id0 + (uint32_t)g, S_RESET_SENSOR, row);
     }
-    if (kp.neighbor == QS_NEIGHBOR_POS_VEL && kp.K > 0) {
+    if (kp.neighbor != QS_NEIGHBOR_NONE && kp.K > 0) {
         float4* xch = reinterpret_cast<float4*>(lds + L().xch);
+        float4* xrot = reinterpret_cast<float4*>(lds + L().xrot);
         xch_put(xch, lane, d.pos, sv);
+        xch_put_rot(kp, xrot, lane, sr);
         lds_sync();
-        neighbor_obs<NPAD, 1>(kp, xch, base, di, 0, d.pos, sv, sel, row);
+        neighbor_obs<NPAD, 1>(kp, xch, xrot, base, di, 0, d.pos, sv, sr, rng, kp.id0 + (uint32_t)g, S_NBR_RNG_RESET, sel, row);
     }
     if (OBST && sel) {
         const float2* myob = otile + el * kp.M;
@@ -1693,6 +1777,10 @@ __global__ __launch_bounds__(reset_geo(NPAD).WGS) void reset_kernel(const KP* __
         store_drone<WIDE>(kp, b, g, d);
 #pragma unroll
         for (int c = 0; c < 3; ++c) b.stale[c * kp.I + g] = sv[c];
+        if (srot) {
+#pragma unroll
+            for (int c = 0; c < 9; ++c) b.stale[(size_t)(3 + c) * kp.I + g] = sr[c];
+        }
         b.done[g] = 0;
         if (kp.stats) {   // QuadrotorEnvMulti.reset zeroes the episode statistics (quadrotor_multi.py:487-509)
 #pragma unroll

@@ -67,7 +67,7 @@ __device__ __forceinline__ uint32_t* snap_word(const KP& kp, const Bufs& b, int 
     n = QS_NI * N;
     if (w < n) { const int f = w / N; return reinterpret_cast<uint32_t*>(b.ist + (size_t)f * kp.I + (size_t)e * N + (w - f * N)); }
     w -= n;
-    n = 3 * N;
+    n = (kp.flavor == QS_FLAVOR_B ? stale_rows(kp.nfeat) : 3) * N;   // stale vel (+ stale rot)
     if (w < n) { const int f = w / N; return reinterpret_cast<uint32_t*>(b.stale + (size_t)f * kp.I + (size_t)e * N + (w - f * N)); }
     w -= n;
     if (w < QS_NE) { *episode = w == QS_E_EPISODE; return reinterpret_cast<uint32_t*>(b.env + (size_t)w * kp.E + e); }

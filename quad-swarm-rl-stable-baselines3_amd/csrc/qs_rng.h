@@ -28,6 +28,8 @@ enum : uint32_t {
     S_SCN = 23, S_SCN_RESET = 24,
     // obstacle domain randomisation, per env (key = drone 0): uniform 0 density choice, 1 size choice
     S_DR = 26,
+    // flavor-B rng3 neighbour obs: 3 uniforms per (drone, slot), block = slot; step obs / reset obs
+    S_NBR_RNG = 27, S_NBR_RNG_RESET = 28,
     UNIF_BIT = 0x80
 };
 

@@ -106,10 +106,10 @@ static int self_obs_dim(int repr) {
     return (repr >= 0 && repr < 7) ? d[repr] : 0;
 }
 
-// floats per visible neighbour (quad_utils.py:40-58) and the flavor-A feature mask
+// floats per visible neighbour (quad_utils.py:40-58) and the feature mask (qs_common.h QS_NF_*)
 static int neighbor_dim(int t) {
-    static const int d[9] = {0, 6, 2, 3, 3, 3, 5, 3, 3};
-    return (t >= 0 && t < 9) ? d[t] : 0;
+    static const int d[13] = {0, 6, 2, 3, 3, 3, 5, 3, 3, 15, 6, 9, 3};
+    return (t >= 0 && t < 13) ? d[t] : 0;
 }
 static int neighbor_feats(int t) {
     using namespace qs;
@@ -122,6 +122,10 @@ static int neighbor_feats(int t) {
         case QS_NEIGHBOR_DIST_SANGLE_SHEADING: return QS_NF_DIST | QS_NF_SANGLE | QS_NF_SHEADING;
         case QS_NEIGHBOR_POS: return QS_NF_POS;
         case QS_NEIGHBOR_NPOS: return QS_NF_NPOS;
+        case QS_NEIGHBOR_POS_VEL_R: return QS_NF_POS | QS_NF_VEL | QS_NF_R;
+        case QS_NEIGHBOR_POS_RZ: return QS_NF_POS | QS_NF_RZ;
+        case QS_NEIGHBOR_POS_VEL_RZ: return QS_NF_POS | QS_NF_VEL | QS_NF_RZ;
+        case QS_NEIGHBOR_RNG3: return QS_NF_RNG;
         default: return 0;
     }
 }
@@ -133,11 +137,13 @@ static int validate(const qs_config* c) {
     if (c->num_agents < 1 || c->num_agents > QS_MAX_AGENTS)
         return fail(QS_E_UNSUPPORTED, "num_agents must be in [1, QS_MAX_AGENTS]");
     if (c->flavor != QS_FLAVOR_B && c->flavor != QS_FLAVOR_A) return fail(QS_E_INVALID, "unknown flavor");
-    if (c->neighbor_obs < 0 || c->neighbor_obs > QS_NEIGHBOR_NPOS) return fail(QS_E_INVALID, "unknown neighbor_obs");
+    if (c->neighbor_obs < 0 || c->neighbor_obs > QS_NEIGHBOR_RNG3) return fail(QS_E_INVALID, "unknown neighbor_obs");
     if (c->flavor == QS_FLAVOR_B) {
         if (c->obs_repr < 0 || c->obs_repr > 2) return fail(QS_E_INVALID, "obs_repr is not a flavor-B repr");
-        if (c->neighbor_obs != QS_NEIGHBOR_NONE && c->neighbor_obs != QS_NEIGHBOR_POS_VEL)
-            return fail(QS_E_UNSUPPORTED, "flavor B implements neighbor_obs none / pos_vel");
+        if (c->neighbor_obs != QS_NEIGHBOR_NONE && c->neighbor_obs != QS_NEIGHBOR_POS_VEL &&
+            c->neighbor_obs < QS_NEIGHBOR_POS)
+            return fail(QS_E_UNSUPPORTED, "flavor B implements neighbor_obs none / pos_vel / pos / npos / pos_vel_R / "
+                                          "pos_Rz / pos_vel_Rz / rng3");
         if (c->use_obstacles) {
             if ((c->scenario < QS_SCEN_OBST_MIX || c->scenario > QS_SCEN_O_STATIC_SAME_GOAL) &&
                 (c->scenario < QS_SCEN_O_SWAP_GOALS || c->scenario > QS_SCEN_O_DYNAMIC_SAME_GOAL))
@@ -164,6 +170,8 @@ static int validate(const qs_config* c) {
         }
     } else {
         if (c->use_obstacles) return fail(QS_E_UNSUPPORTED, "flavor A with obstacles is not implemented");
+        if (c->neighbor_obs > QS_NEIGHBOR_NPOS)
+            return fail(QS_E_UNSUPPORTED, "flavor A does not implement neighbor_obs pos_vel_R / pos_Rz / pos_vel_Rz / rng3");
         if (c->obs_repr < 3 || c->obs_repr > 6) return fail(QS_E_INVALID, "obs_repr is not a flavor-A repr");
         if (c->scenario != QS_SCEN_STATIC_SAME_GOAL && c->scenario != QS_SCEN_DYNAMIC_REPULSIVE &&
             (c->scenario < QS_SCEN_MIX || c->scenario > QS_SCEN_RUN_AWAY))
@@ -194,6 +202,11 @@ static int npad_of(int n);
 static constexpr size_t QS_LDS_MAX = 160 * 1024;
 static size_t shm_bytes(const qs::KP& kp, int npad, bool step, int qb = QS_QB, int qa = QS_QA);
 static int neighbor_dim(int t);
+static int neighbor_feats(int t);
+// rows of the stale buffer: QuadrotorEnvMulti.vel, and for the flavor-B types with an R / Rz part .rot
+static int stale_rows_of(const qs_config* c) {
+    return c->flavor == QS_FLAVOR_B ? qs::stale_rows(neighbor_feats(c->neighbor_obs)) : 3;
+}
 
 // pillar slots per env: the configured count, or the largest domain-randomisation choice
 static int obst_slots(const qs_config* c) {
@@ -217,7 +230,7 @@ static qs_layout make_layout(const qs_config* c) {
     L.env = o; o = al(o + sizeof(int32_t) * QS_NE * E);
     L.env_f = o; o = al(o + sizeof(float) * QS_NENVF * E);
     L.obst = o; o = al(o + sizeof(float) * 2 * (c->use_obstacles ? (size_t)obst_slots(c) : 0) * E);
-    L.stale_vel = o; o = al(o + sizeof(float) * 3 * I);
+    L.stale_vel = o; o = al(o + sizeof(float) * stale_rows_of(c) * I);
     L.obs = o; o = al(o + sizeof(float) * I * od);
     L.term_obs = o; o = al(o + sizeof(float) * I * od);
     L.rew = o; o = al(o + sizeof(float) * I);
@@ -366,6 +379,7 @@ static qs::KP make_kp(const qs_config* c, const qs_layout& L) {
     k.rew_spin = c->rew_spin; k.quadcol = c->rew_quadcol_bin;
     k.spawn_box = c->spawn_box;
     k.flavor = c->flavor;
+    k.nfeat = neighbor_feats(c->neighbor_obs); k.nfd = neighbor_dim(c->neighbor_obs);
     // goal scenarios (flavor B, no obstacles): QS_SCEN_MIX -> 10, QS_SCEN_STATIC_DIFF_GOAL.. -> 1..9
     k.scen_b = -1;
     if (!c->use_obstacles && c->scenario >= QS_SCEN_MIX && c->scenario <= QS_SCEN_RUN_AWAY)
@@ -515,7 +529,7 @@ static int envs_per_block(const qs::KP& kp, int npad, bool step, int qb = QS_QB,
 static size_t shm_bytes(const qs::KP& kp, int npad, bool step, int qb, int qa) {
     const qs::Geo g = launch_geo(kp, npad, step, qb, qa);
     const bool obst = kp.obst != 0;
-    const qs::LdsMap m = qs::lds_map(g, kp.obs_dim, kp.M, obst);
+    const qs::LdsMap m = qs::lds_map(g, kp.obs_dim, kp.M, obst, kp.flavor == QS_FLAVOR_B ? qs::xch_rot_f4(kp.nfeat) : 0);
     return sizeof(float) * (size_t)qs::lds_words(m, g, npad, qs::scen_tables(obst, kp.scen_b));
 }
 
@@ -554,6 +568,19 @@ extern "C" int qs_create(const qs_config* c, int dev, void* ws, qs_handle** out)
         std::vector<float> cr((size_t)c->num_envs, c->capture_radius);
         e = hipMemcpy((char*)h->ws + h->lay.env_f + sizeof(float) * QS_ENVF_CAPTURE * (size_t)c->num_envs, cr.data(),
                       sizeof(float) * cr.size(), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess && stale_rows_of(c) > 3) {
+        // QuadrotorEnvMulti.rot before the first step is the identity (quadrotor_multi.py:92-95): the stale rows
+        // hold it and every env's flags say so (QS_EF_STALE), so the first reset observes it
+        const size_t I = (size_t)h->lay.num_drones;
+        std::vector<float> one(I, 1.f);
+        for (int k = 0; k < 9 && e == hipSuccess; k += 4)
+            e = hipMemcpy((char*)h->ws + h->lay.stale_vel + sizeof(float) * (3 + k) * I, one.data(), sizeof(float) * I,
+                          hipMemcpyHostToDevice);
+        std::vector<int32_t> fl((size_t)c->num_envs, QS_EF_STALE);
+        if (e == hipSuccess)
+            e = hipMemcpy((char*)h->ws + h->lay.env + sizeof(int32_t) * QS_E_FLAGS * (size_t)c->num_envs, fl.data(),
+                          sizeof(int32_t) * fl.size(), hipMemcpyHostToDevice);
     }
     // the initialisation ran on the null stream: complete it before any (possibly non-blocking) stream
     // of the caller touches the workspace
@@ -704,7 +731,7 @@ static int launch_replay(qs_handle* h, bool step, const uint8_t* mask, hipStream
 static size_t snap_words(const qs_config* c, int obs_dim) {
     const size_t M = c->use_obstacles ? (size_t)obst_slots(c) : 0;
     const size_t N = (size_t)c->num_agents;
-    return N * (QS_NF + QS_NI + 3 + (size_t)obs_dim) + QS_NE + QS_NENVF + 2 * M;
+    return N * (QS_NF + QS_NI + (size_t)stale_rows_of(c) + (size_t)obs_dim) + QS_NE + QS_NENVF + 2 * M;
 }
 
 extern "C" int qs_replay_config_default(qs_replay_config* rc, float control_dt) {

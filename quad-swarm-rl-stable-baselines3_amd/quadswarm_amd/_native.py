@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("QUADSWARM_LIB", os.path.join(HERE, "lib", "libquadswarm.so"))
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 MAX_AGENTS = 128
 A_KMAX = 16   # flavor A, more than 64 drones: visible neighbours (qs_flavor_a.h QS_A_KMAX)
 MAX_DR_CHOICES = 8
@@ -25,8 +25,11 @@ OBS_REPR_A = (3, 4, 5, 6)
 SELF_OBS_DIM = {0: 18, 1: 19, 2: 24, 3: 6, 4: 6, 5: 7, 6: 7}
 NEIGHBOR_NONE, NEIGHBOR_POS_VEL = 0, 1
 NEIGHBOR = {"none": 0, "pos_vel": 1, "dist_angle": 2, "dist_sangle": 3, "ndist_nsangle": 4, "dist_angle_heading": 5,
-            "dist_sangle_sheading": 6, "pos": 7, "npos": 8}
-NEIGHBOR_DIM = {0: 0, 1: 6, 2: 2, 3: 3, 4: 3, 5: 3, 6: 5, 7: 3, 8: 3}
+            "dist_sangle_sheading": 6, "pos": 7, "npos": 8, "pos_vel_R": 9, "pos_Rz": 10, "pos_vel_Rz": 11, "rng3": 12}
+NEIGHBOR_DIM = {0: 0, 1: 6, 2: 2, 3: 3, 4: 3, 5: 3, 6: 5, 7: 3, 8: 3, 9: 15, 10: 6, 11: 9, 12: 3}
+# flavor B's types (quadrotor_multi.py:275-319); those with an R / Rz part keep a stale rotation (env.stale_rot)
+NEIGHBOR_B = ("none", "pos_vel", "pos", "npos", "pos_vel_R", "pos_Rz", "pos_vel_Rz", "rng3")
+NEIGHBOR_ROT = ("pos_vel_R", "pos_Rz", "pos_vel_Rz")
 SCENARIO = {"static_same_goal": 0, "dynamic_repulsive": 1, "obst_mix": 2, "o_random": 3, "o_static_same_goal": 4,
             "o_swap_goals": 15, "o_ep_rand_bezier": 16, "o_dynamic_same_goal": 17}
 # flavor B with obstacles: quads_mode -> qs_scenario (scenarios/obstacles/; the dynamic three: ABI 14)

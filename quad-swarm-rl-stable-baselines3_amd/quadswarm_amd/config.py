@@ -236,8 +236,10 @@ class QuadSwarmConfig:
             raise ValueError(f"obs_repr {self.obs_repr!r} does not belong to flavor {self.flavor}")
         if self.neighbor_obs_type not in N.NEIGHBOR:
             raise NotImplementedError(f"neighbor_obs_type {self.neighbor_obs_type!r} not implemented")
-        if self.flavor == "B" and self.neighbor_obs_type not in ("pos_vel", "none"):
-            raise NotImplementedError(f"flavor B implements neighbor_obs_type pos_vel / none")
+        if self.flavor == "B" and self.neighbor_obs_type not in N.NEIGHBOR_B:
+            raise NotImplementedError(f"flavor B implements neighbor_obs_type {' / '.join(N.NEIGHBOR_B)}")
+        if self.flavor == "A" and self.neighbor_obs_type in ("pos_vel_R", "pos_Rz", "pos_vel_Rz", "rng3"):
+            raise NotImplementedError(f"flavor A does not implement neighbor_obs_type {self.neighbor_obs_type!r}")
         if self.flavor == "B" and not self.use_obstacles and self.quads_mode not in N.SCENARIO_B:
             raise NotImplementedError(f"quads_mode {self.quads_mode!r} not implemented for flavor B "
                                       f"({', '.join(N.SCENARIO_B)})")

@@ -62,6 +62,10 @@ class QuadSwarmEnv:
         M = cfg.max_obstacles if cfg.use_obstacles else 0   # pillar slots (an env uses its first QS_E_OBST_M)
         self.obstacles = view(lay.obst, 8 * M * E, torch.float32, (E, M, 2)) if M else None
         self.stale_vel = view(lay.stale_vel, 4 * 3 * I, torch.float32, (3, I))
+        # QuadrotorEnvMulti.rot as a reset sees it, row-major [9, I] (the neighbour types with an R / Rz part only)
+        self.stale_rot = None
+        if cfg.flavor == "B" and cfg.neighbor_obs_type in N.NEIGHBOR_ROT and cfg.k_neighbors > 0:
+            self.stale_rot = view(lay.stale_vel + 4 * 3 * I, 4 * 9 * I, torch.float32, (9, I))
         self.obs = view(lay.obs, 4 * I * od, torch.float32, (I, od))
         self.term_obs = view(lay.term_obs, 4 * I * od, torch.float32, (I, od))
         self.rew = view(lay.rew, 4 * I, torch.float32, (I,))
@@ -294,9 +298,18 @@ def observation_bounds(cfg: QuadSwarmConfig):
         lo.append(np.zeros(1)); hi.append(rd[2] * np.ones(1))
     elif cfg.obs_repr.endswith("wall"):
         lo.append(np.zeros(6)); hi.append(5.0 * np.ones(6))
+    # get_rel_pos_vel_item's parts (quadrotor_single.py:312-326): rxyz, rvxyz, then R (9) or Rz (3) in +-1; rng3 has
+    # the rxyz box
+    t = cfg.neighbor_obs_type
+    nlo, nhi = [-room_range], [room_range]
+    if "vel" in t:
+        nlo.append(-2 * vmax * np.ones(3)); nhi.append(2 * vmax * np.ones(3))
+    nr = 3 if t.endswith("_Rz") else (9 if t.endswith("_R") else 0)
+    if nr:
+        nlo.append(-np.ones(nr)); nhi.append(np.ones(nr))
     for _ in range(cfg.k_neighbors):
-        lo += [-room_range, -2 * vmax * np.ones(3)]
-        hi += [room_range, 2 * vmax * np.ones(3)]
+        lo += nlo
+        hi += nhi
     if cfg.use_obstacles:   # "octmap" (quadrotor_single.py:331)
         lo.append(-10 * np.ones(9)); hi.append(10 * np.ones(9))
     return np.concatenate(lo).astype(np.float32), np.concatenate(hi).astype(np.float32)
