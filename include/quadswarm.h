@@ -640,6 +640,22 @@ int qs_curriculum_step(qs_handle* h, qs_curriculum* d_cur, void* stream);
  * new radius is written to THIS handle's envs. */
 int qs_curriculum_step_all(qs_handle* h, const uint8_t* d_reset_all, int64_t n_all, qs_curriculum* d_cur, void* stream);
 
+/* ---- Headless rendering: selected envs as uint8 RGB frames, drawn on the device from the state buffers by one
+ * kernel (csrc/qs_render.h; DESIGN.md "Rendering" has the picture's contract).  No reference counterpart: the
+ * reference's viewer (gym_art/quadrotor_multi/quadrotor_visualization.py, swarm_rl/sb_render.py) needs a display
+ * and a GL context.  Read-only on the simulation. */
+enum qs_render_view { QS_RENDER_TOPDOWN = 0, QS_RENDER_SIDE = 1, QS_RENDER_FRONT = 2 };   /* (u, v) = (x, y), (x, z), (y, z) */
+typedef struct { int32_t width, height, view, follow; float drone_scale; int32_t reserved[3]; } qs_render_config;
+int qs_render_config_default(qs_render_config* rc);                 /* 256 x 256, topdown, room window, scale 1 */
+/* Host only, no device: validates rc for cfg (view in range, 16 <= width, height <= 2048, width % 4 == 0,
+ * drone_scale finite in (0, 64], the env's primitive list within the LDS budget) and returns height * width * 3. */
+int qs_render_query(const qs_config* cfg, const qs_render_config* rc, size_t* frame_bytes);
+/* Draws envs d_env_ids[0 .. n) (device int32; repeats allowed, order kept) into d_rgb [n, height, width, 3]
+ * (device, 4-byte aligned), asynchronously on `stream`: after a qs_step on the same stream it shows that step's
+ * state.  1 <= n <= 65535.  The ids must lie in [0, num_envs): the caller checks them (quadswarm_amd does, on its
+ * host list); the kernel clamps an id, so a bad one draws another env but never reads out of bounds. */
+int qs_render(qs_handle* h, const qs_render_config* rc, const int32_t* d_env_ids, int32_t n, uint8_t* d_rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1341,3 +1341,69 @@ extern "C" int qs_debug_stamps_h(qs_handle* h, uint64_t* host, size_t n) {
     return QS_OK;
 }
 #endif
+
+// =============================================================================================
+// Headless rendering (qs_render.h): frames of selected envs from the state the step kernels keep
+// =============================================================================================
+#include "qs_render.h"
+
+extern "C" int qs_render_config_default(qs_render_config* rc) {
+    if (!rc) return fail(QS_E_INVALID, "render config is NULL");
+    memset(rc, 0, sizeof *rc);
+    rc->width = 256;
+    rc->height = 256;
+    rc->view = qs::QS_VIEW_TOPDOWN;
+    rc->follow = 0;
+    rc->drone_scale = 1.f;
+    return QS_OK;
+}
+
+// the primitive capacity of a config's env (the kernel sizes its LDS list by the same function)
+static int render_prims(const qs_config* c) {
+    const int m = c->use_obstacles ? obst_slots(c) : 0;
+    return qs::render_max_prims(c->num_agents, m < qs::QS_RD_MAX_OBST ? m : qs::QS_RD_MAX_OBST, c->flavor == QS_FLAVOR_A);
+}
+
+static int render_validate(const qs_config* c, const qs_render_config* rc) {
+    if (!rc) return fail(QS_E_INVALID, "render config is NULL");
+    if (rc->view < 0 || rc->view >= qs::QS_VIEW_N) return fail(QS_E_INVALID, "render view must be 0 (topdown), 1 (side) or 2 (front)");
+    if (rc->width < 16 || rc->width > 2048 || rc->height < 16 || rc->height > 2048)
+        return fail(QS_E_INVALID, "render width and height must be in [16, 2048]");
+    if (rc->width % 4 != 0) return fail(QS_E_INVALID, "render width must be a multiple of 4 (rows are stored as whole dwords)");
+    if (!(rc->drone_scale > 0.f) || !(rc->drone_scale <= 64.f)) return fail(QS_E_INVALID, "render drone_scale must be in (0, 64]");
+    // 64 KB: what a workgroup gets without opting in to more; 128 drones + 64 pillars need 58 KB
+    if (qs::render_lds_bytes(render_prims(c)) > 64 * 1024)
+        return fail(QS_E_UNSUPPORTED, "render: the env's primitive list exceeds the LDS budget");
+    return QS_OK;
+}
+
+extern "C" int qs_render_query(const qs_config* c, const qs_render_config* rc, size_t* frame_bytes) {
+    int r = validate(c);
+    if (!r) r = render_validate(c, rc);
+    if (r) return r;
+    if (!frame_bytes) return fail(QS_E_INVALID, "frame_bytes is NULL");
+    *frame_bytes = (size_t)rc->width * (size_t)rc->height * 3;
+    return QS_OK;
+}
+
+extern "C" int qs_render(qs_handle* h, const qs_render_config* rc, const int32_t* d_env_ids, int32_t n, uint8_t* d_rgb,
+                         void* stream) {
+    if (!h) return fail(QS_E_INVALID, "handle is NULL");
+    if (int r = render_validate(&h->cfg, rc)) return r;
+    if (n < 1 || n > 65535) return fail(QS_E_INVALID, "render: n must be in [1, 65535]");
+    if (!d_env_ids || !d_rgb) return fail(QS_E_INVALID, "render: NULL device pointer");
+    if (((uintptr_t)d_rgb & 3) != 0) return fail(QS_E_INVALID, "render: d_rgb must be 4-byte aligned");
+    QS_HIP(use_device(h));
+    const qs::Bufs b = bufs_of(h);
+    const qs::KP* kpd = (const qs::KP*)((char*)h->ws + h->lay.params);
+    qs::RenderArgs ra;
+    ra.W = rc->width; ra.H = rc->height; ra.view = rc->view; ra.follow = rc->follow ? 1 : 0;
+    ra.drone_scale = rc->drone_scale; ra.n = n;
+    const unsigned tiles = (unsigned)(((ra.W + qs::QS_RD_TW - 1) / qs::QS_RD_TW) * ((ra.H + qs::QS_RD_TH - 1) / qs::QS_RD_TH));
+    const size_t shm = qs::render_lds_bytes(render_prims(&h->cfg));
+    hipLaunchKernelGGL(qs::render_kernel, dim3(tiles, (unsigned)n), dim3(qs::QS_RD_WG), shm, (hipStream_t)stream, kpd,
+                       (const float*)b.st, (const int32_t*)b.ist, (const int32_t*)b.env, (const float*)b.envf,
+                       (const float2*)b.obst, d_env_ids, (uint32_t*)d_rgb, ra);
+    QS_HIP(hipGetLastError());
+    return QS_OK;
+}

@@ -10,6 +10,7 @@ from .params import crazyflie_params, dynamics_constants
 
 __all__ = ["QuadSwarmConfig", "QuadSwarmError", "QuadSwarmEnv", "GpuQuadVecEnv", "make_vec_env",
            "crazyflie_params", "dynamics_constants"]
+__all__ += ["RenderConfig", "PALETTE", "tile_images", "write_png"]
 
 
 def __getattr__(name):  # torch-dependent pieces load lazily
@@ -19,4 +20,7 @@ def __getattr__(name):  # torch-dependent pieces load lazily
     if name in ("GpuQuadVecEnv", "make_vec_env"):
         from . import vec_env
         return getattr(vec_env, name)
+    if name in ("RenderConfig", "PALETTE", "tile_images", "write_png"):
+        from . import render
+        return getattr(render, name)
     raise AttributeError(name)

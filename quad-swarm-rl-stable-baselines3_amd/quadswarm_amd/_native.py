@@ -171,6 +171,14 @@ class QsCurriculum(ctypes.Structure):
                 ("past", ctypes.c_double * CUR_MAX_WINDOW), ("history", ctypes.c_double * CUR_MAX_HIST)]
 
 
+RENDER_VIEWS = {"topdown": 0, "side": 1, "front": 2}   # qs_render_view
+
+
+class QsRenderConfig(ctypes.Structure):
+    """qs_render_config (quadswarm.h)."""
+    _fields_ = [("width", I32), ("height", I32), ("view", I32), ("follow", I32), ("drone_scale", F), ("reserved", I32 * 3)]
+
+
 class QuadSwarmError(RuntimeError):
     pass
 
@@ -189,6 +197,7 @@ EXPORTS = ["qs_abi_version", "qs_last_error", "qs_struct_sizes", "qs_config_defa
            "qs_linear_tanh_x3", "qs_dw_x3_ld", "qs_linear_rows_x3",
            "qs_tanh_grad_stats", "qs_linear_bias_x3", "qs_slab_sum_stats",
            "qs_linear_tanh_cat_x3"]
+EXPORTS += ["qs_render_config_default", "qs_render_query", "qs_render"]
 
 _lib = None
 
@@ -246,6 +255,11 @@ def lib():
         "qs_slab_sum_stats": ([V, I32, ctypes.c_int64, I32, V, V, V, V], I32),
         "qs_linear_tanh_cat_x3": ([V, V, ctypes.c_int64, V, ctypes.c_int64, V, V, I32, V], I32),
     }
+    sig.update({
+        "qs_render_config_default": ([P(QsRenderConfig)], I32),
+        "qs_render_query": ([P(QsConfig), P(QsRenderConfig), P(SZ)], I32),
+        "qs_render": ([V, P(QsRenderConfig), V, I32, V, V], I32),
+    })
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
         fn.argtypes, fn.restype = args, res

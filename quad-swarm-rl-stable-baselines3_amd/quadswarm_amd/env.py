@@ -232,6 +232,36 @@ class QuadSwarmEnv:
         buf = (ctypes.c_uint8 * n).from_buffer_copy(blob[:n])
         N.check(N.lib().qs_set_state(self._h, buf, n, self._stream()), "qs_set_state")
 
+    def render(self, env_ids=None, cfg=None, out=None):
+        """Frames of the envs `env_ids` (a host sequence of env indices, default env 0; repeats allowed, order
+        kept) as a torch.uint8 [n, H, W, 3] tensor on the env's device, drawn by qs_render on the current stream:
+        after a step it shows that step's state, and nothing reaches the host.  cfg: a quadswarm_amd.render.
+        RenderConfig (default 256 x 256 topdown).  out: a contiguous uint8 device tensor of that shape to draw
+        into, so that a render per step allocates nothing but the id list."""
+        from .render import RenderConfig
+        torch = self._torch
+        rc = (cfg or RenderConfig()).to_qs()
+        nb = ctypes.c_size_t()
+        N.check(N.lib().qs_render_query(self.qcfg, ctypes.byref(rc), ctypes.byref(nb)), "qs_render_query")
+        ids = [0] if env_ids is None else [int(i) for i in env_ids]
+        if not ids:
+            raise ValueError("render: env_ids is empty")
+        if min(ids) < 0 or max(ids) >= self.E:
+            raise ValueError(f"render: env_ids must lie in [0, {self.E})")
+        key = tuple(ids)
+        if getattr(self, "_render_ids_key", None) != key:   # the id list lives on the device; re-uploaded when it changes
+            self._render_ids = torch.tensor(ids, dtype=torch.int32, device=self.device)
+            self._render_ids_key = key
+        shape = (len(ids), rc.height, rc.width, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == self.device
+                  and tuple(out.shape) == shape and out.is_contiguous() and out.data_ptr() % 4 == 0):
+            raise ValueError(f"render: out must be a contiguous, 4-byte aligned uint8 tensor {shape} on {self.device}")
+        N.check(N.lib().qs_render(self._h, ctypes.byref(rc), ctypes.c_void_p(self._render_ids.data_ptr()), len(ids),
+                                  ctypes.c_void_p(out.data_ptr()), self._stream()), "qs_render")
+        return out
+
     # structured views (float32 SoA) for tests / debugging
     def drone_fields(self):
         s = self.state

@@ -131,7 +131,9 @@ class GpuQuadVecEnv:
     on every agent row, like the reference's step."""
 
     def __init__(self, cfg: QuadSwarmConfig = None, as_torch=False, device=None, raise_on_nan=True, infos=True,
-                 **cfg_over):
+                 render_mode=None, render_envs=(0,), render_config=None, **cfg_over):
+        if render_mode not in (None, "rgb_array"):
+            raise ValueError("render_mode must be None or 'rgb_array' (there is no window to draw 'human' into)")
         cfg = cfg or QuadSwarmConfig()
         for k, v in cfg_over.items():
             setattr(cfg, k, v)
@@ -153,6 +155,12 @@ class GpuQuadVecEnv:
         self._last_infos = None
         self._actions = None
         self.render_mode = None
+        # render_mode "rgb_array" (SB3's VecEnv.render_mode): render() tiles the frames of the envs render_envs, drawn
+        # on the device by QuadSwarmEnv.render with render_config (a quadswarm_amd.render.RenderConfig)
+        self.render_mode = render_mode
+        self.render_envs = tuple(int(e) for e in render_envs)
+        self.render_config = render_config
+        self._render_buf = None
         self.raise_on_nan = raise_on_nan
         self._nan_last = 0      # the non-finite reward counter as last read
         self._gen = 0           # step counter: lazy infos of an older step refuse to resolve
@@ -285,6 +293,27 @@ class GpuQuadVecEnv:
                                "replay/avg_replayed": float(np.mean(nrep[perm[:n, e], e])) if n else 0,
                                "replay/obst_density": od, "replay/obst_size": osz})
         return out
+
+    # ---- rendering (SB3 VecEnv.get_images / render) ----
+    def get_images(self):
+        """One np.uint8 [H, W, 3] frame per env of render_envs (SB3's VecEnv.get_images, over envs, not agent rows)."""
+        if self._render_buf is None:      # one device buffer for every call
+            self._render_buf = self.env.render(self.render_envs, self.render_config)
+        else:
+            self.env.render(self.render_envs, self.render_config, out=self._render_buf)
+        return list(self._render_buf.cpu().numpy())
+
+    def render(self, mode=None):
+        """SB3's VecEnv.render: None when render_mode is None; the tiled image of render_envs for "rgb_array".  A
+        `mode` other than the env's render_mode is refused, as SB3 warns and returns None ("human" needs a window)."""
+        if self.render_mode is None:
+            return None
+        if mode is not None and mode != self.render_mode:
+            import warnings
+            warnings.warn(f"render(mode={mode!r}) differs from the env's render_mode {self.render_mode!r}: not drawn")
+            return None
+        from .render import tile_images
+        return tile_images(self.get_images())
 
     def counters(self):
         """The step kernels' non-finite guard counters (qs_counters) since creation or reset_counters()."""
