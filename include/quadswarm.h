@@ -445,6 +445,66 @@ int qs_replay_enable(qs_handle* h, const qs_replay_config* rc, void* d_workspace
 int qs_replay_disable(qs_handle* h);
 int qs_replay_buffers_get(qs_handle* h, qs_replay_buffers* out);
 
+/* ---- Reward shaping wrapper on device: QuadsRewardShapingWrapper (swarm_rl/env_wrappers/reward_shaping.py:19-123,
+ *      built around every flavor-B env by swarm_rl/env_wrappers/quad_utils.py:73-94).  Flavor B with step_infos = 1
+ *      (and episode_stats = 1 when use_obstacles = 1).
+ * Per drone: fp64 sums of the step's eight rew_info rows over the running episode (:69-76); per env: sums of the raw
+ * actions and their squares (:53, :100-106), the episode's step count and the env's own three collision coefficients
+ * (:55-61, :110-118).  At an episode end every drone of the env gets a row of QS_SH_* columns (its last finished
+ * episode), which is also added into a running total so a reader can difference two reads.  With anneal_steps > 0 the
+ * collision coefficients start at 0 and are set at each env's episode end to min(final * S / anneal_steps, final) for
+ * that env only, final = the handle's coefficients and S = the value of qs_shaping_set_training_steps; the step's
+ * reward buffer is corrected to the env's coefficients (DESIGN.md "Reward shaping").  Runs as one more kernel inside
+ * qs_step / qs_step_n / qs_step_blocks / qs_reset once enabled, on the same stream. */
+typedef struct qs_shaping_config {
+    double anneal_steps;            /* anneal_collision_steps (quad_utils.py:80-89); 0 = no annealing */
+} qs_shaping_config;
+
+/* columns of a qs_shaping_buffers.row / .tot row (fp64) */
+enum qs_shaping_col {
+    QS_SH_SUM = 0,                  /* 8 columns: the episode's sums of rew_info rows QS_RI_DIST .. QS_RI_OBST (QS_RI_PROX
+                                       at the step's scale, i.e. with the handle's quadcol_bin_smooth_max) */
+    QS_SH_COEF = 8,                 /* 3: quadcol_bin, quadcol_bin_smooth_max, quadcol_bin_obst in force during the episode */
+    QS_SH_ANNEAL = 11,              /* 3: the same for the env's next episode (z_anneal_*, :117-118) */
+    QS_SH_S = 14,                   /* approx_total_training_steps at the episode end (:92-93) */
+    QS_SH_TRUE_REWARD = 15,         /* dt (-sum DIST) + 1000 sum QUADCOL (:79-85) */
+    QS_SH_ACT_MEAN = 16,            /* 4: mean of action component k over the env's drones and steps (:100-105) */
+    QS_SH_ACT_STD = 20,             /* 4: its population standard deviation (:104) */
+    QS_SH_LEN = 24,                 /* steps of the episode */
+    QS_SH_SCEN = 25,                /* the env's scenario AFTER the step (QS_ES_SCEN's convention; :95-98 read
+                                       scenario.name() after the in-step reset, quadrotor_multi.py:836) */
+    QS_SH_REW = 26,                 /* the episode's weighted reward terms summed (SB3's ep_rew_mean): base coefficients
+                                       as at the episode end, collision coefficients as in force */
+    QS_NSH = 28
+};
+
+typedef struct qs_shaping_buffers { /* device pointers, valid while shaping is enabled */
+    double* acc;                    /* [QS_NRI, I] running sums of the step's rew_info rows                    */
+    double* coef;                   /* [3, E] the env's collision coefficients for its NEXT step              */
+    double* coef_used;              /* [3, E] the coefficients the last step's rewards were formed with        */
+    double* act;                    /* [8, E] sum a_k (rows 0-3) and sum a_k^2 (rows 4-7) over drones and steps */
+    int32_t* steps;                 /* [E] steps of the running episode                                        */
+    double* row;                    /* [I, QS_NSH] the last finished episode of each drone                     */
+    double* tot;                    /* [I, QS_NSH] sums of every row ever written                              */
+    int64_t* tot_n;                 /* [I] their count                                                         */
+    double* S;                      /* [1] approx_total_training_steps                                         */
+} qs_shaping_buffers;
+
+int qs_shaping_config_default(qs_shaping_config* sc);                /* anneal_steps = 0 */
+int qs_shaping_workspace_bytes(qs_handle* h, const qs_shaping_config* sc, size_t* bytes);
+/* Initialises the shaping state in d_workspace (caller-owned device memory of qs_shaping_workspace_bytes, 256-byte
+ * aligned; NULL: the library allocates it), synchronously: sums 0, coef 0 with annealing, else the handle's
+ * coefficients.  QS_E_UNSUPPORTED for flavor A (its infos carry no rewards: quadrotor_single_rewards.py:457 makes
+ * reward_shaping.py:79 raise KeyError at the first episode end); QS_E_INVALID without step_infos, and with
+ * use_obstacles = 1 without episode_stats = 1: QS_SH_SCEN is read from the env row QS_E_SC_MODE, which the obstacle
+ * kernels keep for every scenario only together with the episode stats. */
+int qs_shaping_enable(qs_handle* h, const qs_shaping_config* sc, void* d_workspace);
+int qs_shaping_disable(qs_handle* h);
+int qs_shaping_buffers_get(qs_handle* h, qs_shaping_buffers* out);
+/* training_info["approx_total_training_steps"] (:92): one device scalar written on `stream`, read by the launches
+ * after it on that stream, replays of a captured graph included. */
+int qs_shaping_set_training_steps(qs_handle* h, double S, void* stream);
+
 /* Generalized advantage estimation over a device-resident rollout (replaces stable_baselines3
  * RolloutBuffer.compute_returns_and_advantage, the PPO of swarm_rl/sb_train.py:53-64).  Arrays are
  * [n_steps, n_cols] fp32 / u8, time-major; episode_starts[t] = done of step t-1; last_* = after the

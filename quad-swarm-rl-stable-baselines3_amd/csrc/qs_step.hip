@@ -39,6 +39,7 @@
 #include "qs_gae.h"
 #include "qs_curriculum.h"
 #include "qs_replay.h"
+#include "qs_shaping.h"
 #include "qs_error.h"
 
 // =============================================================================================
@@ -61,6 +62,11 @@ struct qs_handle {
     bool rws_owned = false;
     qs::RBufs rb{};
     qs::RP rp{};
+    // reward shaping (qs_shaping_enable): one device allocation holding every SBufs array
+    void* sws = nullptr;
+    bool sws_owned = false;
+    qs::SBufs sb{};
+    qs::SP sp{};
 };
 
 static thread_local std::string g_err;
@@ -615,9 +621,16 @@ static void replay_free(qs_handle* h) {
     if (h->ws) (void)rargs_sync(h);
 }
 
+static void shaping_free(qs_handle* h) {
+    if (h->sws && h->sws_owned) (void)hipFree(h->sws);
+    h->sws = nullptr;
+    h->sb = qs::SBufs{};
+}
+
 extern "C" int qs_destroy(qs_handle* h) {
     if (!h) return QS_OK;
     replay_free(h);
+    shaping_free(h);
     if (h->owns_ws && h->ws) {
         hipError_t e = hipFree(h->ws);
         delete h;
@@ -865,11 +878,150 @@ extern "C" int qs_replay_buffers_get(qs_handle* h, qs_replay_buffers* o) {
     return QS_OK;
 }
 
+// the shaping wrapper after the step / reset (and replay) kernel (qs_shaping.h)
+static int launch_shaping(qs_handle* h, bool step, const float* act, const uint8_t* mask, hipStream_t s) {
+    qs::Bufs b = bufs_of(h);
+    b.act = act;
+    b.mask = mask;
+    const qs::KP* kpd = (const qs::KP*)((char*)h->ws + h->lay.params);
+    const int epb = qs::SH_WG / h->kp.N;   // whole envs per workgroup
+    const dim3 grid((unsigned)((h->kp.E + epb - 1) / epb)), block(qs::SH_WG);
+    if (step) hipLaunchKernelGGL(qs::shaping_kernel<true>, grid, block, 0, s, kpd, b, h->sb, h->sp);
+    else hipLaunchKernelGGL(qs::shaping_kernel<false>, grid, block, 0, s, kpd, b, h->sb, h->sp);
+    QS_HIP(hipGetLastError());
+    return QS_OK;
+}
+
+struct ShapingOffsets { size_t acc, coef, coef_used, act, steps, row, tot, tot_n, S, total; };
+static ShapingOffsets shaping_offsets(const qs_handle* h) {
+    const size_t E = (size_t)h->cfg.num_envs, I = (size_t)h->lay.num_drones;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    ShapingOffsets o;
+    o.acc = 0;
+    o.coef = al(o.acc + 8 * QS_NRI * I);
+    o.coef_used = al(o.coef + 8 * 3 * E);
+    o.act = al(o.coef_used + 8 * 3 * E);
+    o.steps = al(o.act + 8 * qs::SH_NQ * E);
+    o.row = al(o.steps + 4 * E);
+    o.tot = al(o.row + 8 * QS_NSH * I);
+    o.tot_n = al(o.tot + 8 * QS_NSH * I);
+    o.S = al(o.tot_n + 8 * I);
+    o.total = al(o.S + 8);
+    return o;
+}
+
+static int shaping_check(const qs_handle* h, const qs_shaping_config* sc) {
+    if (!h || !sc) return fail(QS_E_INVALID, "NULL argument");
+    if (h->cfg.flavor != QS_FLAVOR_B)
+        return fail(QS_E_UNSUPPORTED, "reward shaping is flavor B: flavor A's infos carry no rewards "
+                                      "(quadrotor_single_rewards.py:457), the reference's wrapper raises KeyError on them");
+    if (!h->cfg.step_infos) return fail(QS_E_INVALID, "reward shaping needs a handle created with step_infos = 1 (it reads rew_info)");
+    // QS_SH_SCEN is the env row QS_E_SC_MODE; with obstacles the step and reset kernels keep it for every scenario
+    // only while they keep the episode stats (qs_flavor_b.h: the o_random / o_static_same_goal / mix reset writes it
+    // under kp.stats), so a row would name static_same_goal instead
+    if (h->cfg.use_obstacles && !h->cfg.episode_stats)
+        return fail(QS_E_INVALID, "reward shaping with obstacles needs a handle created with episode_stats = 1 "
+                                  "(the row's scenario id is the env's QS_E_SC_MODE word, kept with the stats)");
+    if (!(sc->anneal_steps >= 0.0) || !std::isfinite(sc->anneal_steps))
+        return fail(QS_E_INVALID, "anneal_steps must be finite and >= 0");
+    return QS_OK;
+}
+
+extern "C" int qs_shaping_config_default(qs_shaping_config* sc) {
+    if (!sc) return fail(QS_E_INVALID, "NULL argument");
+    sc->anneal_steps = 0.0;
+    return QS_OK;
+}
+
+extern "C" int qs_shaping_workspace_bytes(qs_handle* h, const qs_shaping_config* sc, size_t* bytes) {
+    int r = shaping_check(h, sc);
+    if (r) return r;
+    if (!bytes) return fail(QS_E_INVALID, "NULL argument");
+    *bytes = shaping_offsets(h).total;
+    return QS_OK;
+}
+
+extern "C" int qs_shaping_enable(qs_handle* h, const qs_shaping_config* sc, void* d_workspace) {
+    int r = shaping_check(h, sc);
+    if (r) return r;
+    if (d_workspace && ((uintptr_t)d_workspace & 255) != 0) return fail(QS_E_INVALID, "workspace must be 256-byte aligned");
+    QS_HIP(use_device(h));
+    QS_HIP(hipDeviceSynchronize());
+    shaping_free(h);
+    const ShapingOffsets off = shaping_offsets(h);
+    hipError_t e = hipSuccess;
+    if (d_workspace) {
+        h->sws = d_workspace;
+        h->sws_owned = false;
+    } else {
+        e = hipMalloc(&h->sws, off.total);
+        if (e != hipSuccess) { h->sws = nullptr; return fail(QS_E_HIP, std::string("hipMalloc(shaping): ") + hipGetErrorString(e)); }
+        h->sws_owned = true;
+    }
+    char* w = (char*)h->sws;
+    h->sb.acc = (double*)(w + off.acc);
+    h->sb.coef = (double*)(w + off.coef);
+    h->sb.coef_used = (double*)(w + off.coef_used);
+    h->sb.act = (double*)(w + off.act);
+    h->sb.steps = (int32_t*)(w + off.steps);
+    h->sb.row = (double*)(w + off.row);
+    h->sb.tot = (double*)(w + off.tot);
+    h->sb.tot_n = (long long*)(w + off.tot_n);
+    h->sb.S = (double*)(w + off.S);
+    h->sp.anneal = sc->anneal_steps;
+    // dt as the reference's Python float: the config carries 1 / sim_freq in fp32; an integer sim_freq (200) gives
+    // back the fp64 quotient (make_kp does the same for control_freq)
+    double freq = 1.0 / (double)h->cfg.dt;
+    h->sp.dt = fabs(freq - (double)llround(freq)) < 1e-4 ? 1.0 / (double)llround(freq) : (double)h->cfg.dt;
+    // rew_coeff of every env: 0 with annealing (quad_utils.py:80-83), else the handle's values
+    const size_t E = (size_t)h->cfg.num_envs;
+    const double cg[3] = {(double)h->kp.quadcol, (double)h->kp.prox_max, (double)h->kp.quadcol_obst};
+    std::vector<double> coef(3 * E);
+    for (int c = 0; c < 3; ++c)
+        for (size_t x = 0; x < E; ++x) coef[(size_t)c * E + x] = sc->anneal_steps > 0.0 ? 0.0 : cg[c];
+    e = hipMemset(h->sws, 0, off.total);
+    if (e == hipSuccess) e = hipMemcpy(h->sb.coef, coef.data(), 8 * coef.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(h->sb.coef_used, coef.data(), 8 * coef.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();   // null-stream init complete before any caller stream
+    if (e != hipSuccess) {
+        shaping_free(h);
+        return fail(QS_E_HIP, std::string("shaping init: ") + hipGetErrorString(e));
+    }
+    return QS_OK;
+}
+
+extern "C" int qs_shaping_disable(qs_handle* h) {
+    if (!h) return fail(QS_E_INVALID, "handle is NULL");
+    QS_HIP(use_device(h));
+    QS_HIP(hipDeviceSynchronize());
+    shaping_free(h);
+    return QS_OK;
+}
+
+extern "C" int qs_shaping_buffers_get(qs_handle* h, qs_shaping_buffers* o) {
+    if (!h || !o) return fail(QS_E_INVALID, "NULL argument");
+    if (!h->sws) return fail(QS_E_INVALID, "reward shaping is not enabled");
+    o->acc = h->sb.acc; o->coef = h->sb.coef; o->coef_used = h->sb.coef_used; o->act = h->sb.act;
+    o->steps = h->sb.steps; o->row = h->sb.row; o->tot = h->sb.tot; o->tot_n = (int64_t*)h->sb.tot_n; o->S = h->sb.S;
+    return QS_OK;
+}
+
+extern "C" int qs_shaping_set_training_steps(qs_handle* h, double S, void* stream) {
+    if (!h) return fail(QS_E_INVALID, "handle is NULL");
+    if (!h->sws) return fail(QS_E_INVALID, "reward shaping is not enabled");
+    QS_HIP(use_device(h));
+    // a one-lane kernel with S as its argument: stream-ordered, no host memory read later, capturable
+    hipLaunchKernelGGL(qs::shaping_set_scalar, dim3(1), dim3(1), 0, (hipStream_t)stream, h->sb.S, S);
+    QS_HIP(hipGetLastError());
+    return QS_OK;
+}
+
 extern "C" int qs_reset(qs_handle* h, const uint8_t* d_mask, void* stream) {
     if (!h) return fail(QS_E_INVALID, "handle is NULL");
     QS_HIP(use_device(h));
     int rc = launch(h, false, nullptr, d_mask, (hipStream_t)stream);
     if (rc == QS_OK && h->rws) rc = launch_replay(h, false, d_mask, (hipStream_t)stream);
+    if (rc == QS_OK && h->sws) rc = launch_shaping(h, false, nullptr, d_mask, (hipStream_t)stream);
     return rc;
 }
 
@@ -887,15 +1039,20 @@ extern "C" int qs_step(qs_handle* h, const float* d_actions, void* stream) {
     if (int rc = check_actions(h, d_actions)) return rc;
     QS_HIP(use_device(h));
     // with replay on, the flavor-B step kernel runs the wrapper in its tail (no second launch)
-    return launch(h, true, d_actions, nullptr, (hipStream_t)stream);
+    int rc = launch(h, true, d_actions, nullptr, (hipStream_t)stream);
+    if (rc == QS_OK && h->sws) rc = launch_shaping(h, true, d_actions, nullptr, (hipStream_t)stream);
+    return rc;
 }
 
 extern "C" int qs_step_n(qs_handle* h, const float* d_actions, int steps, void* stream) {
     if (steps < 1) return fail(QS_E_INVALID, "qs_step_n: steps < 1");
     if (int rc = check_actions(h, d_actions)) return rc;
     QS_HIP(use_device(h));
-    for (int i = 0; i < steps; ++i)
+    for (int i = 0; i < steps; ++i) {
         if (int rc = launch(h, true, d_actions, nullptr, (hipStream_t)stream)) return rc;
+        if (h->sws)
+            if (int rc = launch_shaping(h, true, d_actions, nullptr, (hipStream_t)stream)) return rc;
+    }
     return QS_OK;
 }
 
@@ -906,8 +1063,11 @@ extern "C" int qs_step_blocks(qs_handle* const* hs, int n, const float* const* d
         if (hs[i]->device != hs[0]->device) return fail(QS_E_INVALID, "qs_step_blocks: handles on different devices");
     }
     QS_HIP(use_device(hs[0]));
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < n; ++i) {
         if (int rc = launch(hs[i], true, d_actions[i], nullptr, (hipStream_t)streams[i])) return rc;
+        if (hs[i]->sws)
+            if (int rc = launch_shaping(hs[i], true, d_actions[i], nullptr, (hipStream_t)streams[i])) return rc;
+    }
     return QS_OK;
 }
 

@@ -143,6 +143,20 @@ R_ACTIVE, R_SAVED, R_CK_N, R_CK_HEAD, R_BUF_N, R_BUF_IDX, R_LAST_ADD, R_EPISODES
 R_HIST_N, R_HIST_HEAD, R_RESTORED, R_PUSHED, NR = 10, 11, 12, 13, 14
 
 
+class QsShapingConfig(ctypes.Structure):
+    _fields_ = [("anneal_steps", ctypes.c_double)]
+
+
+class QsShapingBuffers(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("acc", "coef", "coef_used", "act", "steps", "row", "tot", "tot_n", "S")]
+
+
+# qs_shaping_col: columns of a shaping row (fp64)
+SH_SUM, SH_COEF, SH_ANNEAL, SH_S, SH_TRUE_REWARD, SH_ACT_MEAN, SH_ACT_STD = 0, 8, 11, 14, 15, 16, 20
+SH_LEN, SH_SCEN, SH_REW, NSH = 24, 25, 26, 28
+SH_COEF_NAMES = ("quadcol_bin", "quadcol_bin_smooth_max", "quadcol_bin_obst")   # order of the 3-vectors
+
+
 ATTN_MAX_TOWERS = 2
 ATTN_NCOLMAX = 6          # qs_attn_train.colmax rows (QS_ATTN_NCOLMAX)
 
@@ -198,6 +212,8 @@ EXPORTS = ["qs_abi_version", "qs_last_error", "qs_struct_sizes", "qs_config_defa
            "qs_tanh_grad_stats", "qs_linear_bias_x3", "qs_slab_sum_stats",
            "qs_linear_tanh_cat_x3"]
 EXPORTS += ["qs_render_config_default", "qs_render_query", "qs_render"]
+EXPORTS += ["qs_shaping_config_default", "qs_shaping_workspace_bytes", "qs_shaping_enable", "qs_shaping_disable",
+            "qs_shaping_buffers_get", "qs_shaping_set_training_steps"]
 
 _lib = None
 
@@ -259,6 +275,13 @@ def lib():
         "qs_render_config_default": ([P(QsRenderConfig)], I32),
         "qs_render_query": ([P(QsConfig), P(QsRenderConfig), P(SZ)], I32),
         "qs_render": ([V, P(QsRenderConfig), V, I32, V, V], I32),
+    })
+    sig.update({
+        "qs_shaping_config_default": ([P(QsShapingConfig)], I32),
+        "qs_shaping_workspace_bytes": ([V, P(QsShapingConfig), P(SZ)], I32),
+        "qs_shaping_enable": ([V, P(QsShapingConfig), V], I32), "qs_shaping_disable": ([V], I32),
+        "qs_shaping_buffers_get": ([V, P(QsShapingBuffers)], I32),
+        "qs_shaping_set_training_steps": ([V, ctypes.c_double, V], I32),
     })
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

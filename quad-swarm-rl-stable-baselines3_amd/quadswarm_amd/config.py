@@ -78,6 +78,11 @@ class QuadSwarmConfig:
     # which GpuQuadVecEnv builds infos[i]["rewards"] / infos[i]["goal_dist"].  Off for the raw env (the bench's
     # step does not pay for it); GpuQuadVecEnv turns it on (infos=True) ----
     step_infos: bool = False
+    # ---- QuadsRewardShapingWrapper on the device (swarm_rl/env_wrappers/reward_shaping.py:19-123, built by
+    # quad_utils.py:73-94 around every flavor-B env): per-episode reward sums, true_reward, action statistics and,
+    # with anneal_collision_steps > 0, the per-env annealing of the collision coefficients.  Turns step_infos on ----
+    reward_shaping: bool = False
+    anneal_collision_steps: float = 0.0           # acts with reward_shaping only (the wrapper does the annealing)
 
     @classmethod
     def c4(cls, num_envs=4096, num_agents=8, **over):
@@ -146,7 +151,8 @@ class QuadSwarmConfig:
             obst_density_max=g("obst_density_max", "quads_obst_density_max", default=0.2),
             obst_size_random=bool(g("obst_size_random", "quads_obst_size_random", default=False)),
             obst_size_min=g("obst_size_min", "quads_obst_size_min", default=0.3),
-            obst_size_max=g("obst_size_max", "quads_obst_size_max", default=0.6))
+            obst_size_max=g("obst_size_max", "quads_obst_size_max", default=0.6),
+            anneal_collision_steps=float(g("anneal_collision_steps", default=0.0) or 0.0))
         if flavor == "A":
             # sb_train wraps the env in ExperienceReplayWrapper(env, 0.5, ...) when cfg.use_replay_buffer
             # (sb3_quad_env.py:43-45)
@@ -271,6 +277,14 @@ class QuadSwarmConfig:
             # itself).  There is no reference behaviour to reproduce, so the build refuses it the same way.
             raise KeyError("rew_crash: the reference's flavor-A env cannot run the experience-replay wrapper "
                            "(quadrotor_multi_rewards.py:872 reads a reward the flavor-A step does not report)")
+        if self.reward_shaping and self.flavor != "B":
+            # flavor A's per-drone infos carry an empty "rewards" dict (quadrotor_single_rewards.py:457), so the
+            # reference's wrapper raises at the first episode end (reward_shaping.py:79); sb3_quad_env.py does not
+            # build it
+            raise KeyError("rewraw_main: the reference's flavor-A env cannot run QuadsRewardShapingWrapper "
+                           "(reward_shaping.py:79 reads a reward the flavor-A step does not report)")
+        if not self.anneal_collision_steps >= 0.0:
+            raise ValueError("anneal_collision_steps must be >= 0")
         if not 0.0 <= self.replay_buffer_sample_prob <= 1.0:
             raise ValueError("replay_buffer_sample_prob must be in [0, 1]")
         if not 1 <= self.num_agents <= N.MAX_AGENTS:
@@ -348,6 +362,7 @@ class QuadSwarmConfig:
                 c.dr_num_sizes = len(sizes)
                 for i, v in enumerate(sizes):
                     c.dr_sizes[i] = float(v)
-        c.episode_stats = 1 if self.episode_stats else 0
-        c.step_infos = 1 if self.step_infos else 0
+        # with obstacles the shaping row's scenario id is an env word the kernels keep with the episode stats
+        c.episode_stats = 1 if (self.episode_stats or (self.reward_shaping and self.use_obstacles)) else 0
+        c.step_infos = 1 if (self.step_infos or self.reward_shaping) else 0
         return c

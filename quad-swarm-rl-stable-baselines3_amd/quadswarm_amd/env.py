@@ -84,10 +84,14 @@ class QuadSwarmEnv:
         self._coeff = {"pos": r.get("pos", 1.0), "effort": r.get("effort", 0.05), "crash": r.get("crash", 1.0),
                        "orient": r.get("orient", 1.0), "spin": r.get("spin", 0.1),
                        "quadcol_bin": float(cfg.collision_reward), "quadcol_bin_obst": float(cfg.obst_collision_reward)}
+        self._smooth_max = float(cfg.collision_smooth_max_penalty)
         self._torch = torch
         self.replay = None
         if cfg.replay_buffer_sample_prob > 0:
             self.enable_replay(cfg.replay_buffer_sample_prob)
+        self.shaping = None
+        if cfg.reward_shaping:
+            self.enable_reward_shaping(cfg.anneal_collision_steps)
 
     # ------------------------------------------------------------------------------------------
     def enable_replay(self, sample_prob=0.75, **over):
@@ -125,6 +129,41 @@ class QuadSwarmEnv:
         return {"replay/replay_rate": ri[N.R_REPLAYED] / ep,
                 "replay/new_episode_rate": (ri[N.R_EPISODES] - ri[N.R_REPLAYED]) / ep,
                 "replay/replay_buffer_size": ri[N.R_BUF_N].copy()}
+
+    # ------------------------------------------------------------------------------------------
+    def enable_reward_shaping(self, anneal_collision_steps=0.0):
+        """QuadsRewardShapingWrapper on device (swarm_rl/env_wrappers/reward_shaping.py:19-123): per-episode sums of
+        the reward terms, true_reward, the episode's action statistics and, with anneal_collision_steps > 0, the
+        per-env annealing of quadcol_bin / quadcol_bin_smooth_max / quadcol_bin_obst from 0 to the env's values
+        (quad_utils.py:80-89), run by qs_step / qs_reset from now on.  Needs per-step infos (config step_infos).
+        env.shaping holds zero-copy views of its state; quadswarm_amd.stats.shaping_infos turns a row into the
+        wrapper's additions to infos."""
+        sc = N.QsShapingConfig()
+        N.check(N.lib().qs_shaping_config_default(ctypes.byref(sc)), "qs_shaping_config_default")
+        sc.anneal_steps = float(anneal_collision_steps)
+        nb = ctypes.c_size_t()
+        N.check(N.lib().qs_shaping_workspace_bytes(self._h, ctypes.byref(sc), ctypes.byref(nb)), "qs_shaping_workspace_bytes")
+        raw = self._torch.empty(nb.value + 256, dtype=self._torch.uint8, device=self.device)
+        off = (-raw.data_ptr()) % 256
+        ws = raw[off:off + nb.value]
+        self._torch.cuda.synchronize(self.device)   # qs_shaping_enable initialises it synchronously
+        N.check(N.lib().qs_shaping_enable(self._h, ctypes.byref(sc), ctypes.c_void_p(ws.data_ptr())), "qs_shaping_enable")
+        sb = N.QsShapingBuffers()
+        N.check(N.lib().qs_shaping_buffers_get(self._h, ctypes.byref(sb)), "qs_shaping_buffers_get")
+        self.shaping_config, self._shaping_ws = sc, ws
+        self.shaping = _shaping_views(self._torch, ws, sb, self.E, self.I)
+
+    def disable_reward_shaping(self):
+        self._torch.cuda.synchronize(self.device)
+        N.check(N.lib().qs_shaping_disable(self._h), "qs_shaping_disable")
+        self.shaping = None
+
+    def set_training_steps(self, steps):
+        """training_info["approx_total_training_steps"] of the wrapper (reward_shaping.py:92): a device scalar
+        written on the current stream; the annealing schedule and z_approx_total_training_steps read it at each
+        episode end, inside replays of a captured graph too."""
+        N.check(N.lib().qs_shaping_set_training_steps(self._h, float(steps), self._stream()),
+                "qs_shaping_set_training_steps")
 
     # ------------------------------------------------------------------------------------------
     def _stream(self):
@@ -197,10 +236,17 @@ class QuadSwarmEnv:
         N.check(N.lib().qs_set_param(self._h, key.encode(), float(value)), "qs_set_param")
         if key in self._COEFF_PARAMS:
             self._coeff[self._COEFF_PARAMS[key]] = float(value)
+        if key == "quadcol_bin_smooth_max":
+            self._smooth_max = float(value)
 
     def reward_coefficients(self):
         """The reward coefficients of the next step (rew_coeff + quadcol_bin / quadcol_bin_obst), float64."""
         return dict(self._coeff)
+
+    def shaping_coefficients(self):
+        """reward_coefficients() plus quadcol_bin_smooth_max: what quadswarm_amd.stats.shaping_infos and
+        infos.reward_columns_env need next to an env's own collision coefficients (env.shaping["coef_used"])."""
+        return dict(self._coeff, quadcol_bin_smooth_max=self._smooth_max)
 
     def get_param(self, key):
         v = ctypes.c_double()
@@ -298,6 +344,22 @@ def _replay_views(torch, ws, rb, rc, E):
                 perm=view(rb.perm, rc.buffer_size * E, torch.int32, (rc.buffer_size, E)),
                 nrep=view(rb.nrep, rc.buffer_size * E, torch.int32, (rc.buffer_size, E)),
                 store=view(rb.store, E * slots * W, torch.int32, (E, slots, W)), snap_words=W, slots=slots)
+
+
+def _shaping_views(torch, ws, sb, E, I):
+    """Zero-copy torch views of the shaping state (qs_shaping_buffers) inside the torch-owned workspace."""
+    base = ws.data_ptr()
+
+    def view(ptr, n, dtype, shape):
+        o = int(ptr) - base
+        nbytes = n * torch.tensor([], dtype=dtype).element_size()
+        return ws[o:o + nbytes].view(dtype).view(*shape)
+    f64 = torch.float64
+    return dict(acc=view(sb.acc, N.NRI * I, f64, (N.NRI, I)), coef=view(sb.coef, 3 * E, f64, (3, E)),
+                coef_used=view(sb.coef_used, 3 * E, f64, (3, E)), act=view(sb.act, 8 * E, f64, (8, E)),
+                steps=view(sb.steps, E, torch.int32, (E,)), row=view(sb.row, I * N.NSH, f64, (I, N.NSH)),
+                tot=view(sb.tot, I * N.NSH, f64, (I, N.NSH)), tot_n=view(sb.tot_n, I, torch.int64, (I,)),
+                S=view(sb.S, 1, f64, (1,)))
 
 
 def observation_bounds(cfg: QuadSwarmConfig):

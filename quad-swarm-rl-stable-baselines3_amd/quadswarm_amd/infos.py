@@ -41,9 +41,21 @@ def reward_columns_b(comp, coeff, dt, use_obstacles=False):
     return out
 
 
+def reward_columns_env(comp, coeff, coef_used, num_agents, dt, use_obstacles=False):
+    """reward_columns_b with every env's own collision coefficients (reward shaping with annealing: rew_coeff is per
+    multi-env, swarm_rl/env_wrappers/reward_shaping.py:110-118).  coef_used [3, E]: quadcol_bin,
+    quadcol_bin_smooth_max, quadcol_bin_obst the step's rewards were formed with (env.shaping["coef_used"]); coeff:
+    env.shaping_coefficients(), whose quadcol_bin_smooth_max is the scale of comp's proximity row."""
+    c = np.array(comp, dtype=np.float64)
+    cu = np.repeat(np.asarray(coef_used, dtype=np.float64), num_agents, axis=1)    # [3, I]
+    g_sm = float(coeff.get("quadcol_bin_smooth_max", 0.0))
+    c[N.RI_PROX] = c[N.RI_PROX] * (cu[1] / g_sm) if g_sm != 0.0 else 0.0
+    return reward_columns_b(c, dict(coeff, quadcol_bin=cu[0], quadcol_bin_obst=cu[2]), dt, use_obstacles)
+
+
 def rewards_dict(cols, i):
     """infos[i]["rewards"] of row i from reward_columns_b's columns (python floats, like the reference's)."""
     return {k: float(v[i]) for k, v in cols.items()}
 
 
-__all__ = ["REWARD_KEYS_B", "REWARD_KEYS_OBST", "COEFF_KEYS", "reward_columns_b", "rewards_dict"]
+__all__ = ["REWARD_KEYS_B", "REWARD_KEYS_OBST", "COEFF_KEYS", "reward_columns_b", "reward_columns_env", "rewards_dict"]

@@ -526,6 +526,10 @@ class PPOTrainer:
         self.last_obs = None
         self.last_done = torch.zeros(env.I, dtype=torch.uint8, device=self.device)
         self.last_values = torch.zeros(env.I, dtype=torch.float32, device=self.device)
+        # with the reward shaping wrapper on (env.shaping): the episodes that ended during the last rollout
+        # (_episode_records) and the running totals they are differenced from
+        self.episode_records = {}
+        self._shaping_seen = None
         # the rollout's policy evaluations through the fused HIP attention encoders (policy_fused.py) where
         # the policy has that encoder; the update keeps the torch module (autograd)
         self.fused = None
@@ -565,6 +569,12 @@ class PPOTrainer:
         from .callbacks import StepContext
         for cb in callbacks:
             cb.on_rollout_start(self)
+        shaping = getattr(self.env, "shaping", None) is not None
+        if shaping:
+            # approx_total_training_steps of the wrapper (reward_shaping.py:92): the annealing schedule's clock.
+            # Parity unpinned: the reference's value is sample_factory's counter, which is not installed here to be
+            # compared with; num_timesteps (every rank's agent steps so far) is this trainer's equivalent
+            self.env.set_training_steps(self.num_timesteps)
         for t in range(self.cfg.n_steps):
             st.obs[t].copy_(self.last_obs)
             actions, values, logp = fwd(st.obs[t])
@@ -584,7 +594,11 @@ class PPOTrainer:
                 for cb in callbacks:
                     go = cb.on_step(ctx) is not False and go
                 if not go:
+                    if shaping:
+                        self._episode_records()   # the episodes this partial rollout finished
                     return False
+        if shaping:
+            self._episode_records()
         self.last_values.copy_(fwd.predict_values(self.last_obs).view(-1))
         if self.fused is not None:
             self.fused.check_inputs()   # x3: the rollout's observations stayed inside the split-f16 range
@@ -593,6 +607,31 @@ class PPOTrainer:
         for cb in callbacks:
             cb.on_rollout_end(self)
         return True
+
+    def _episode_records(self):
+        """self.episode_records of the episodes that ended since the last call, from ONE host read of the shaping
+        wrapper's running totals (env.shaping tot / tot_n: sums of every finished episode's row, and their count)
+        differenced against the previous read; sums and counts are all-reduced over the group when distributed.
+        rollout/ep_rew_mean is SB3's (the episode's summed reward terms), ep_true_reward_mean the reference's
+        true_reward (reward_shaping.py:78-85)."""
+        sh = self.env.shaping
+        cols = torch.tensor([NAT.SH_TRUE_REWARD, NAT.SH_LEN, NAT.SH_REW], device=sh["tot"].device)
+        cur = torch.cat([sh["tot"].index_select(1, cols).sum(0), sh["tot_n"].sum().double().view(1)])
+        if self.distributed:
+            import torch.distributed as dist
+            if dist.get_backend(self.group) != "nccl":
+                cur = cur.cpu()
+            dist.all_reduce(cur, group=self.group)
+        cur = cur.cpu()
+        prev = self._shaping_seen if self._shaping_seen is not None else torch.zeros_like(cur)
+        self._shaping_seen = cur
+        d = (cur - prev).tolist()
+        n = d[3]
+        self.episode_records = {"rollout/episodes": int(n)}
+        if n > 0:
+            self.episode_records.update({"rollout/ep_true_reward_mean": d[0] / n, "rollout/ep_len_mean": d[1] / n,
+                                         "rollout/ep_rew_mean": d[2] / n})
+        return self.episode_records
 
     def train(self, max_updates=None):
         """PPO.train: n_epochs over shuffled minibatches of the flattened rollout (max_updates cuts the
@@ -701,6 +740,9 @@ class PPOTrainer:
                     pass
         if getattr(env, "replay", None) is not None:
             sh["replay_ws"] = env._replay_ws.cpu().clone()
+        if getattr(env, "shaping", None) is not None:
+            sh["shaping_ws"] = env._shaping_ws.cpu().clone()
+            sh["shaping_seen"] = self._shaping_seen
         return sh
 
     def _gather_shards(self, shard):
@@ -783,6 +825,9 @@ class PPOTrainer:
             env.set_state(bytes(sh["env_state"].numpy().tobytes()))
         if "replay_ws" in sh:
             env._replay_ws.copy_(sh["replay_ws"].to(env._replay_ws.device))
+        if "shaping_ws" in sh:
+            env._shaping_ws.copy_(sh["shaping_ws"].to(env._shaping_ws.device))
+            self._shaping_seen = sh.get("shaping_seen")
         if sh["last_obs"] is not None:
             obs = getattr(env, "obs", None)
             if obs is None:

@@ -61,3 +61,40 @@ def episode_extra_stats(row, use_obstacles=False):
         d[f"metric/{name}"] = r[col]
         d[f"{sc}/{name}"] = r[col]
     return d
+
+
+def shaping_infos(row, coeff, dt, use_obstacles=False, annealing=False):
+    """What QuadsRewardShapingWrapper adds to a finished agent's info (swarm_rl/env_wrappers/reward_shaping.py:78-118)
+    from its shaping row (sequence of the QS_SH_* columns, fp64; env.shaping["row"][i]): (true_reward, the dict
+    merged into episode_extra_stats).  coeff: env.shaping_coefficients() -- the base coefficients and the handle's
+    collision coefficients (its quadcol_bin_smooth_max is the scale of the row's proximity sum); dt:
+    the simulation step.  The per-key sums are infos.reward_columns_b of the raw sums: that function is linear, so
+    it maps sums to sums, with the collision coefficients that were in force during the episode (QS_SH_COEF).
+    stats["rewraw_main"] is the true reward (:86), "<scenario.name()>/rew_pos|rew_crash" carry the scenario the env
+    holds AFTER the step (:95-98 run after the in-step reset, quadrotor_multi.py:836), and z_anneal_* appear with
+    annealing only (:110-118)."""
+    import numpy as np
+
+    from . import _native as N
+    from .infos import reward_columns_b
+    r = np.asarray(row, dtype=np.float64)
+    comp = r[N.SH_SUM:N.SH_SUM + N.NRI].copy()
+    c_bin, c_sm, c_obst = (float(x) for x in r[N.SH_COEF:N.SH_COEF + 3])
+    g_sm = float(coeff.get("quadcol_bin_smooth_max", 0.0))
+    comp[N.RI_PROX] = comp[N.RI_PROX] * (c_sm / g_sm) if g_sm != 0.0 else 0.0
+    cols = reward_columns_b(comp[:, None], dict(coeff, quadcol_bin=c_bin, quadcol_bin_obst=c_obst), dt, use_obstacles)
+    cum = {k: float(v[0]) for k, v in cols.items()}
+    true_reward = cum["rewraw_main"] + 1000 * cum.get("rewraw_quadcol", 0)
+    cum["rewraw_main"] = true_reward
+    stats = dict(cum)
+    stats["z_approx_total_training_steps"] = float(r[N.SH_S])
+    sc = "Scenario_" + SCENARIO_NAMES.get(int(r[N.SH_SCEN]), "static_same_goal")
+    for k in ("rew_pos", "rew_crash"):
+        stats[f"{sc}/{k}"] = cum[k]
+    for k in range(4):
+        stats[f"z_action{k}_mean"] = float(r[N.SH_ACT_MEAN + k])
+        stats[f"z_action{k}_std"] = float(r[N.SH_ACT_STD + k])
+    if annealing:
+        for k, name in enumerate(N.SH_COEF_NAMES):
+            stats[f"z_anneal_{name}"] = float(r[N.SH_ANNEAL + k])
+    return true_reward, stats

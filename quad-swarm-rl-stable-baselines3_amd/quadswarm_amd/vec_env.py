@@ -66,16 +66,18 @@ class StepInfos(Sequence):
     device buffers it reads are the step's; a later first read raises RuntimeError).  Rows read in time stay
     valid: their terminal_observation is a copy of the finished agents' rows, not a view of the env's buffer."""
 
-    def __init__(self, n, done_rows=(), term=None, extra=None, rewards=None, goal_dist=None, resolve=None):
+    def __init__(self, n, done_rows=(), term=None, extra=None, rewards=None, goal_dist=None, true_reward=None,
+                 resolve=None):
         self._n = n
         self._resolve = resolve
         self._d = None
         self._m = {}       # row -> the dict handed out for it (memoised)
         if resolve is None:
-            self._build(done_rows, term, extra, rewards, goal_dist)
+            self._build(done_rows, term, extra, rewards, goal_dist, true_reward)
 
-    def _build(self, done_rows, term, extra, rewards, goal_dist):
-        """term: the terminal observations of the finished rows, in done_rows order."""
+    def _build(self, done_rows, term, extra, rewards, goal_dist, true_reward=None):
+        """term: the terminal observations of the finished rows, in done_rows order; true_reward: with reward
+        shaping on, their info["true_reward"] (reward_shaping.py:85)."""
         self._rows = np.asarray(done_rows, dtype=np.int64)
         self._rewards, self._gd = rewards, goal_dist
         self._d = {}
@@ -83,6 +85,8 @@ class StepInfos(Sequence):
             self._d[r] = {"terminal_observation": term[k], "TimeLimit.truncated": False}
             if extra is not None:
                 self._d[r]["episode_extra_stats"] = extra[k]
+            if true_reward is not None:
+                self._d[r]["true_reward"] = true_reward[k]
 
     def _ready(self):
         if self._d is None:
@@ -228,14 +232,16 @@ class GpuQuadVecEnv:
                 self._nan_pending = True
             gen = self._gen
             comp = self.env.rew_info.clone() if self.env.rew_info is not None else None
+            cu = self.env.shaping["coef_used"].clone() if self.env.shaping is not None else None
 
             def resolve():
                 if gen != self._gen:
                     raise RuntimeError("GpuQuadVecEnv infos of an older step: read them before the next step_wait")
                 rows_t = torch.nonzero(d).flatten()
                 rows = rows_t.cpu().numpy()
-                return (rows, term[rows_t].clone(), self._episode_extra_stats(rows) if len(rows) else None) + \
-                    self._step_info_columns(comp)
+                extra = self._episode_extra_stats(rows) if len(rows) else None
+                return (rows, term[rows_t].clone(), extra) + self._step_info_columns(comp, cu) + \
+                    (self._shaping_merge(rows, extra),)
             infos = StepInfos(self.num_envs, resolve=resolve)
             self._last_infos = infos
             return obs, rew, d, infos
@@ -246,19 +252,40 @@ class GpuQuadVecEnv:
         self._reset_infos, self._last_infos = self._reset_infos_of(rows), None
         extra = self._episode_extra_stats(rows) if len(rows) else None
         term_np = term[torch.as_tensor(rows, device=term.device)].cpu().numpy() if len(rows) else None
-        cols = self._step_info_columns(self.env.rew_info)
+        cols = self._step_info_columns(self.env.rew_info,
+                                       self.env.shaping["coef_used"] if self.env.shaping is not None else None)
         return obs.cpu().numpy(), rew.cpu().numpy(), d.cpu().numpy(), StepInfos(self.num_envs, rows, term_np, extra,
-                                                                               *cols)
+                                                                               *cols, self._shaping_merge(rows, extra))
 
-    def _step_info_columns(self, comp):
-        """(flavor-B reward columns, flavor-A goal distances) of a step's reward components (None when off)."""
+    def _step_info_columns(self, comp, coef_used=None):
+        """(flavor-B reward columns, flavor-A goal distances) of a step's reward components (None when off).
+        coef_used: with reward shaping on, the envs' own collision coefficients of that step [3, E]."""
         if comp is None:
             return None, None
         c = comp.cpu().numpy()
         if self.cfg.flavor == "A":
             return None, c[N.RI_GOAL_DIST]
-        from .infos import reward_columns_b
+        from .infos import reward_columns_b, reward_columns_env
+        if coef_used is not None:
+            return reward_columns_env(c, self.env.shaping_coefficients(), coef_used.cpu().numpy(), self.agents_per_env,
+                                      float(self.cfg.dt), self.cfg.use_obstacles), None
         return reward_columns_b(c, self.env.reward_coefficients(), float(self.cfg.dt), self.cfg.use_obstacles), None
+
+    def _shaping_merge(self, rows, extra):
+        """With reward shaping on: merges the wrapper's per-episode stats into the finished rows'
+        episode_extra_stats (reward_shaping.py:87-118) and returns their true_reward values; else None."""
+        if self.env.shaping is None or extra is None or len(rows) == 0:
+            return None
+        from .stats import shaping_infos
+        t = self.env._torch
+        sh = self.env.shaping["row"][t.as_tensor(rows, device=self.env.device, dtype=t.long)].cpu().numpy()
+        coeff, ann = self.env.shaping_coefficients(), self.env.shaping_config.anneal_steps > 0
+        out = []
+        for k in range(len(rows)):
+            tr, st = shaping_infos(sh[k], coeff, float(self.cfg.dt), self.cfg.use_obstacles, annealing=ann)
+            extra[k].update(st)
+            out.append(tr)
+        return out
 
     def _episode_extra_stats(self, rows):
         """infos[i]["episode_extra_stats"] of the finished rows: the env's counters (quadrotor_multi.py:739-831)
@@ -366,6 +393,9 @@ class GpuQuadVecEnv:
         idx = list(self._get_indices(indices))
         if method_name in ("set_param", "set_reward_coeff"):
             self.env.set_param(*method_args, **method_kwargs)
+            return [None] * len(idx)
+        if method_name == "set_training_steps":
+            self.env.set_training_steps(*method_args, **method_kwargs)
             return [None] * len(idx)
         if method_name == "set_capture_radius":
             self.env.set_capture_radius(*method_args, env_indices=None if indices is None else idx)

@@ -11,6 +11,8 @@ Stand-in semantics:
     run as plain NumPy.  numba's RNG is replaced by NumPy's global RNG (numba.random = np.random).
   * gymnasium: Env/Wrapper base classes, spaces.Box, utils.seeding.np_random.
   * cv2, bezier: empty modules.  sample_factory.utils.utils.experiment_dir: stub.
+  * sample_factory.envs.env_utils: TrainingInfoInterface (a training_info dict) and RewardShapingInterface, the two
+    mix-ins of the reward shaping wrapper.
   * gym_art.quadrotor_multi.quadrotor_multi_visualization: stub (pyglet/OpenGL).
 """
 import os
@@ -92,6 +94,16 @@ _SHIMS = {
     "sample_factory/__init__.py": "",
     "sample_factory/utils/__init__.py": "",
     "sample_factory/utils/utils.py": "def experiment_dir(cfg=None, **k):\n    return '/tmp'\n",
+    # what swarm_rl/env_wrappers/reward_shaping.py mixes in: a training_info dict the runner fills, and a marker class
+    "sample_factory/envs/__init__.py": "",
+    "sample_factory/envs/env_utils.py": """
+        class TrainingInfoInterface:
+            def __init__(self):
+                self.training_info = dict()
+        class RewardShapingInterface:
+            def __init__(self):
+                pass
+    """,
 }
 
 _installed = None
