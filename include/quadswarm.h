@@ -668,6 +668,35 @@ int qs_colstats(const float* G, int64_t R, int32_t H, const float* row_w, const 
                 int32_t nbr_off, int32_t B, int32_t K, int32_t nd, int32_t nx, float* part_max, float* part_sum,
                 float* part_x, int32_t n_parts, void* stream);
 
+/* Fused no-grad forward of the obstacle policies' multi-head attention encoder (QuadMultiHeadAttentionEncoder,
+ * swarm_rl/models/quad_multi_model.py:125-200, up to its LayerNorm; csrc/qs_policy_mha.h) on the split-f16 matrix
+ * cores: neighbor_embed_layer and obstacle_embed_layer (two Linear + Tanh each) give two tokens per agent, which go
+ * through the 4-head MultiHeadAttention (attention_layer.py:10-54, d_k = d_v = H, temperature sqrt(H)), fc, the
+ * residual and the LayerNorm (eps 1e-6).  One launch, up to QS_ATTN_MAX_TOWERS towers; H 128 or 256; every pointer is
+ * device memory; w_*p are packed as for qs_attn_embed_x3 (quadswarm_amd.policy_fused.pack_mfma_weight_x3). */
+typedef struct qs_mha_tower {
+    const void* w_e1p;     /* packed [H, 80]: [neighbor_embed_layer[0].weight (nbr_width) | 0 .. | obstacle_embed_layer[0]
+                              .weight at column 64 (obst_dim) | 0 ..] */
+    const float* b_n1;     /* [H] neighbor_embed_layer[0].bias */
+    const float* b_o1;     /* [H] obstacle_embed_layer[0].bias */
+    const void* w_n2p;     /* packed neighbor_embed_layer[2].weight */
+    const void* w_o2p;     /* packed obstacle_embed_layer[2].weight */
+    const float* b_n2;
+    const float* b_o2;
+    const void* w_qp;      /* 4 packed [H, H] blocks each, head h first: w_qs.weight[hH:(h+1)H, :], */
+    const void* w_kp;      /*   w_ks.weight[hH:(h+1)H, :],                                            */
+    const void* w_vp;      /*   w_vs.weight[hH:(h+1)H, :],                                            */
+    const void* w_fcp;     /*   fc.weight[:, hH:(h+1)H]                                               */
+    const float* ln_g;     /* [H] layer_norm.weight */
+    const float* ln_b;     /* [H] layer_norm.bias */
+    float* out;            /* [B, 2H] out: the normalised tokens, attn_embed.view(batch, -1) */
+} qs_mha_tower;
+/* obs: [B, obs_stride] rows: agent b's neighbour block is obs[b * obs_stride + self_dim ..), nbr_width (<= 64) wide,
+ * followed by its obst_dim (<= 16) obstacle values.  |obs| < 4094 and max_row |w_vs|_1 < 4094 (the split-f16 ranges:
+ * the caller checks both).  Asynchronous on `stream`. */
+int qs_mha_encoder_x3(const float* d_obs, int32_t obs_stride, int32_t self_dim, int32_t nbr_width, int32_t obst_dim,
+                      int32_t B, int32_t H, const qs_mha_tower* towers, int32_t n_towers, void* stream);
+
 /* sb_train's capture-radius curriculum on the device (ABI 11; replaces CurriculumCallback._on_step,
  * swarm_rl/custom_callbacks.py:441-468, which SB3 runs after every VecEnv step).  Flavor A.  The callback's state
  * is a qs_curriculum in DEVICE memory; qs_curriculum_step, enqueued after a qs_step, records the outcome of every

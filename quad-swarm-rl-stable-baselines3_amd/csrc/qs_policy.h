@@ -35,6 +35,8 @@
 //   qs_policy_x3.h    : the split-f16 tile and layer, attn_embed_x3_body (the rollout's and the update's embedding),
 //                       the rollout's attn_pool_x3_kernel, the feed_forward linear_tanh_x3_kernel
 //   qs_policy_train.h : the update's attn_pool_train_x3_kernel (the forward with saves), the backward, dW, statistics
+// (qs_policy_mha.h, the multi-head attention encoder of the obstacle policies, builds on qs_policy_x3.h in a translation
+// unit of its own, qs_policy_mha.hip.)
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>

@@ -168,6 +168,12 @@ class QsAttnTower(ctypes.Structure):
                [("b_a3", F), ("out", ctypes.c_void_p)]
 
 
+class QsMhaTower(ctypes.Structure):
+    """qs_mha_tower (device pointers of one multi-head attention encoder tower, quadswarm.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("w_e1p", "b_n1", "b_o1", "w_n2p", "w_o2p", "b_n2", "b_o2", "w_qp", "w_kp",
+                                                "w_vp", "w_fcp", "ln_g", "ln_b", "out")]
+
+
 class QsAttnTrain(ctypes.Structure):
     """qs_attn_train (the PPO update's saved activations and gradients of one tower, quadswarm.h)."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("e1", "a1", "a2", "v1", "h", "w", "dout", "dem", "w_v2tp", "w_v1tp",
@@ -210,7 +216,7 @@ EXPORTS = ["qs_abi_version", "qs_last_error", "qs_struct_sizes", "qs_config_defa
            "qs_attn_bwd1_x3", "qs_attn_bwd2_x3", "qs_attn_dw_x3", "qs_attn_dw0_x3", "qs_colmax_reduce", "qs_colstats",
            "qs_linear_tanh_x3", "qs_dw_x3_ld", "qs_linear_rows_x3",
            "qs_tanh_grad_stats", "qs_linear_bias_x3", "qs_slab_sum_stats",
-           "qs_linear_tanh_cat_x3"]
+           "qs_linear_tanh_cat_x3", "qs_mha_encoder_x3"]
 EXPORTS += ["qs_render_config_default", "qs_render_query", "qs_render"]
 EXPORTS += ["qs_shaping_config_default", "qs_shaping_workspace_bytes", "qs_shaping_enable", "qs_shaping_disable",
             "qs_shaping_buffers_get", "qs_shaping_set_training_steps"]
@@ -270,6 +276,7 @@ def lib():
         "qs_linear_bias_x3": ([V, ctypes.c_int64, I32, V, ctypes.c_int64, V, V, I32, V], I32),
         "qs_slab_sum_stats": ([V, I32, ctypes.c_int64, I32, V, V, V, V], I32),
         "qs_linear_tanh_cat_x3": ([V, V, ctypes.c_int64, V, ctypes.c_int64, V, V, I32, V], I32),
+        "qs_mha_encoder_x3": ([V, I32, I32, I32, I32, I32, I32, P(QsMhaTower), I32, V], I32),
     }
     sig.update({
         "qs_render_config_default": ([P(QsRenderConfig)], I32),

@@ -12,6 +12,11 @@ Per step, for the actor and the critic tower at once (one launch per stage):
 The result is the same function as the torch module (fp32 throughout; only the summation order of the
 GEMMs differs: tests/test_gpu_policy_fused.py bounds it).  Training (the PPO update with autograd) keeps
 the torch module.
+
+A policy built with encoder_type "attention" (the obstacle runs' QuadMultiHeadAttentionEncoder, quad_multi_model.py:
+125-200) is the second family: with precision "x3" one launch of qs_mha_encoder_x3 (csrc/qs_policy_mha.h) takes both
+towers from the observations to the two normalised attention tokens per agent; the self encoder and feed_forward
+stay in torch (the self encoder's second layer on qs_linear_tanh_x3 where it fits).  tests/test_gpu_policy_mha.py.
 """
 import ctypes
 
@@ -31,6 +36,8 @@ def pack_mfma_weight(w):
 X3_SW = 256.0   # weight scale of the split-f16 packing (csrc/qs_policy_x3.h X3_SW)
 X3_SIN = 16.0   # raw-observation scale of the x3 layer-0 inputs (csrc/qs_policy_x3.h X3_SIN)
 F16_MAX = 65504.0
+X3_SC = 16.0    # context scale of the multi-head attention encoder (csrc/qs_policy_mha.h X3_SC)
+MHA_NBW, MHA_OBW = 64, 16   # its layer-0 columns: the neighbour block, the obstacle values (csrc/qs_policy_mha.h)
 
 
 def pack_mfma_weight_x3(w):
@@ -174,6 +181,9 @@ def linear_rows_x3(x, row_scale, packed, n_out, out=None):
 def supports(policy):
     """Can the fused kernels evaluate this policy's encoders?"""
     c = policy.cfg
+    if c.encoder_type == "attention":   # QuadMultiHeadAttentionEncoder on qs_mha_encoder_x3 (csrc/qs_policy_mha.h)
+        return (c.nonlinearity == "tanh" and c.rnn_size in (128, 256) and
+                1 <= c.neighbor_obs_dim * c.num_use_neighbor_obs <= MHA_NBW and 1 <= c.obstacle_obs_dim <= MHA_OBW)
     return (c.neighbor_encoder_type == "attention" and c.num_use_neighbor_obs >= 1 and
             c.neighbor_hidden_size in (128, 256) and 1 <= c.neighbor_obs_dim <= 16 and
             c.num_use_neighbor_obs <= 64 and c.self_obs_dim + c.neighbor_obs_dim <= 32 and c.nonlinearity == "tanh")
@@ -199,7 +209,9 @@ class FusedRolloutPolicy:
             raise ValueError("fused rollout forward: needs the tanh attention encoder with hidden size 128 or 256")
         self.policy = policy
         self.cfg = policy.cfg
-        self.H = self.cfg.neighbor_hidden_size
+        # the multi-head attention encoder family (encoder_type "attention", csrc/qs_policy_mha.h): x3 only
+        self.mha = self.cfg.encoder_type == "attention"
+        self.H = self.cfg.rnn_size if self.mha else self.cfg.neighbor_hidden_size
         self.K = self.cfg.num_use_neighbor_obs
         self.nd = self.cfg.neighbor_obs_dim
         self.so = self.cfg.self_obs_dim
@@ -207,12 +219,14 @@ class FusedRolloutPolicy:
         self.L = NAT.lib()
         self.B = None
         self.packed = None
-        self.towers = (NAT.QsAttnTower * NAT.ATTN_MAX_TOWERS)()
+        self.towers = ((NAT.QsMhaTower if self.mha else NAT.QsAttnTower) * NAT.ATTN_MAX_TOWERS)()
 
     # ---- weights / buffers ----
     def refresh(self):
         """Re-pack the weights.  x3: a weight outside the split-f16 range (|w| >= 255.9) would become +-inf; the
         towers are then packed (and evaluated) in fp32 until a later refresh finds every weight in range again."""
+        if self.mha:
+            return self._refresh_mha()
         prec = self.precision
         if prec == "x3":
             lim = F16_MAX / X3_SW
@@ -292,6 +306,88 @@ class FusedRolloutPolicy:
             t.w_a1ep, t.w_a2p, t.b_a2, t.w_a3 = p(w["w_a1ep"]), p(w["w_a2p"]), p(w["b_a2"]), p(w["w_a3"])
             t.b_a3, t.out = w["b_a3"], p(self.out[i])
 
+    # ---- the multi-head attention encoder family ----
+    def _refresh_mha(self):
+        """precision "fp32": the torch module evaluates this family (it has no fp32-MFMA kernels).  "x3": the kernel,
+        unless a weight is outside the split-f16 range (|w| >= 255.9) or the context bound max_row |w_vs|_1 (|ctx| <=
+        it, since the tokens are tanh outputs) reaches 65504 / X3_SC; then the torch module, until a later refresh."""
+        prec = "torch"
+        if self.precision == "x3":
+            prec = "x3"
+            stats = []
+            for enc in self.encs:
+                at = enc.attention_layer
+                ms = (enc.neighbor_embed_layer[0], enc.neighbor_embed_layer[2], enc.obstacle_embed_layer[0],
+                      enc.obstacle_embed_layer[2], at.w_qs, at.w_ks, at.w_vs, at.fc)
+                stats.append(torch.stack((torch.stack([m.weight.detach().abs().amax() for m in ms]).amax(),
+                                          at.w_vs.weight.detach().abs().sum(dim=1).amax())))
+            big, vnorm = torch.stack(stats).amax(dim=0).tolist()   # one host read
+            if not (big < F16_MAX / X3_SW and vnorm < F16_MAX / X3_SC):   # NaN fails too
+                import warnings
+                warnings.warn(f"x3 rollout encoders: max |w| = {big:.4g} (limit {F16_MAX / X3_SW:.4g}), max row |w_vs|_1 = "
+                              f"{vnorm:.4g} (limit {F16_MAX / X3_SC:.4g}): outside the split-f16 range; evaluating in torch")
+                prec = "torch"
+        self.packed_precision = prec
+        if prec == "torch":
+            self.packed = [{} for _ in self.encs]
+            return
+        H, nbw, od = self.H, self.nd * self.K, self.cfg.obstacle_obs_dim
+        packed = []
+        for enc in self.encs:
+            ne, oe, at = enc.neighbor_embed_layer, enc.obstacle_embed_layer, enc.attention_layer
+            w_e1 = torch.zeros(H, MHA_NBW + MHA_OBW, dtype=torch.float32, device=ne[0].weight.device)
+            w_e1[:, :nbw] = ne[0].weight.detach()                       # [neighbour block | 0 | obstacle values | 0]
+            w_e1[:, MHA_NBW:MHA_NBW + od] = oe[0].weight.detach()
+            rows = lambda lin: [lin.weight[h * H:(h + 1) * H] for h in range(4)]  # noqa: E731  head h's projection
+            pk = pack_mfma_weights_x3([w_e1, ne[2].weight, oe[2].weight] + rows(at.w_qs) + rows(at.w_ks) + rows(at.w_vs)
+                                      + [at.fc.weight[:, h * H:(h + 1) * H] for h in range(4)])   # 18 [H, H]: one batch
+            w = dict(w_e1p=pk[0], w_n2p=pk[1], w_o2p=pk[2], w_qp=torch.stack(pk[3:7]), w_kp=torch.stack(pk[7:11]),
+                     w_vp=torch.stack(pk[11:15]), w_fcp=torch.stack(pk[15:19]),
+                     b_n1=ne[0].bias.detach(), b_o1=oe[0].bias.detach(), b_n2=ne[2].bias.detach(),
+                     b_o2=oe[2].bias.detach(), ln_g=at.layer_norm.weight.detach(), ln_b=at.layer_norm.bias.detach())
+            se = enc.self_embed_layer
+            if self_l2_supported(se) and float(se[2].weight.detach().abs().amax()) < F16_MAX / X3_SW:
+                w.update(w_s2p=pack_linear_x3(se[2].weight.detach()), b_s2=se[2].bias.detach().contiguous())
+            packed.append(w)
+        self.packed = packed
+        self._bind_mha()
+
+    def _bind_mha(self):
+        if self.packed_precision != "x3" or self.B is None:
+            return
+        for i, w in enumerate(self.packed):
+            t = self.towers[i]
+            for name in ("w_e1p", "b_n1", "b_o1", "w_n2p", "w_o2p", "b_n2", "b_o2", "w_qp", "w_kp", "w_vp", "w_fcp",
+                         "ln_g", "ln_b"):
+                assert w[name].is_contiguous()
+                setattr(t, name, w[name].data_ptr())
+            t.out = self.out[i].data_ptr()
+
+    def _mha_tokens(self, obs):
+        """[T, B, 2H]: both towers' normalised attention tokens (QuadMultiHeadAttentionEncoder.tokens)."""
+        if self.packed_precision != "x3":
+            return [enc.tokens(obs) for enc in self.encs]
+        B = obs.shape[0]
+        if self.B != B:
+            self.B = B
+            self.out = torch.empty(len(self.encs), B, 2 * self.H, dtype=torch.float32, device=obs.device)
+            self._bind_mha()
+        m = obs.abs().amax()   # layer 0's range check, on the device (read by check_inputs)
+        self._obs_absmax = m if self._obs_absmax is None else torch.maximum(self._obs_absmax, m)
+        st = ctypes.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        NAT.check(self.L.qs_mha_encoder_x3(ctypes.c_void_p(obs.data_ptr()), obs.shape[1], self.so, self.nd * self.K,
+                                           self.cfg.obstacle_obs_dim, B, self.H, self.towers, len(self.encs), st),
+                  "qs_mha_encoder_x3")
+        return self.out
+
+    def _encode_mha(self, enc, obs, tokens, w):
+        se = enc.self_embed_layer
+        if "w_s2p" in w:   # the second Linear + Tanh (tanh inputs) as one kernel
+            s = linear_tanh_x3(se[1](se[0](obs[:, :self.so])), w["w_s2p"], w["b_s2"])
+        else:
+            s = se(obs[:, :self.so])
+        return enc.feed_forward(torch.cat((s, tokens), dim=1))
+
     # ---- forward ----
     @torch.no_grad()
     def neighbor_encodings(self, obs):
@@ -301,6 +397,8 @@ class FusedRolloutPolicy:
         B = obs.shape[0]
         if self.packed is None:
             self.refresh()
+        if self.mha:   # this family's encodings are its two attention tokens, [T, B, 2H]
+            return self._mha_tokens(obs)
         if self.B != B:
             self._alloc(B, obs.device)
         so, H, K = self.so, self.H, self.K
@@ -321,6 +419,8 @@ class FusedRolloutPolicy:
         return self.out
 
     def _encode(self, enc, obs, nbr_out, w=None):
+        if self.mha:
+            return self._encode_mha(enc, obs, nbr_out, w)
         so, na = self.so, enc.all_neighbor_obs_size
         se = enc.self_encoder
         if w is not None and "w_s2p" in w:   # x3: the second Linear + Tanh (tanh inputs) as one kernel

@@ -55,6 +55,7 @@ class PolicyConfig:
     decoder_mlp_layers: List[int] = field(default_factory=list)
     log_std_init: float = 0.0
     act_dim: int = 2
+    encoder_type: str = "mlp"          # mlp (QuadMultiEncoder) | attention (QuadMultiHeadAttentionEncoder), global_cfg.py:51
 
     @classmethod
     def for_env(cls, env_cfg, **over):
@@ -222,6 +223,75 @@ class QuadMultiEncoder(nn.Module):
         return self.feed_forward(x)
 
 
+class MultiHeadAttention(nn.Module):
+    """attention_layer.py:10-54 as the encoder below uses it (self-attention, no mask): per-head projections without
+    bias, softmax(q k^T / sqrt(d_k)) v per head, the heads concatenated through fc, plus the input, LayerNorm(eps 1e-6)."""
+
+    def __init__(self, n_head, d_model, d_k, d_v):
+        super().__init__()
+        self.n_head, self.d_k, self.d_v = n_head, d_k, d_v
+        self.w_qs = nn.Linear(d_model, n_head * d_k, bias=False)
+        self.w_ks = nn.Linear(d_model, n_head * d_k, bias=False)
+        self.w_vs = nn.Linear(d_model, n_head * d_v, bias=False)
+        self.fc = nn.Linear(n_head * d_v, d_model, bias=False)
+        self.layer_norm = nn.LayerNorm(d_model, eps=1e-6)
+
+    def forward(self, x):
+        """x [B, L, d_model] -> (the normalised tokens [B, L, d_model], the softmax weights [B, n_head, L, L])."""
+        B, L, _ = x.shape
+        heads = lambda lin, d: lin(x).view(B, L, self.n_head, d).transpose(1, 2)  # noqa: E731  [B, n_head, L, d]
+        q, k, v = heads(self.w_qs, self.d_k), heads(self.w_ks, self.d_k), heads(self.w_vs, self.d_v)
+        attn = torch.softmax(torch.matmul(q / self.d_k ** 0.5, k.transpose(2, 3)), dim=-1)
+        ctx = torch.matmul(attn, v).transpose(1, 2).reshape(B, L, self.n_head * self.d_v)
+        return self.layer_norm(self.fc(ctx) + x), attn
+
+
+class QuadMultiHeadAttentionEncoder(nn.Module):
+    """quad_multi_model.py:125-200, the encoder of the obstacle runs (encoder_type "attention"): self, neighbour-block
+    and obstacle observations each through two Linear + act of rnn_size; the neighbour and obstacle embeddings as two
+    tokens through the 4-head MultiHeadAttention (d_k = d_v = rnn_size); feed_forward Linear(3 rnn_size -> 2 rnn_size)
+    + Tanh on [self | token 0 | token 1].  Parameter names are the reference's."""
+
+    N_HEAD = 4
+
+    def __init__(self, cfg: PolicyConfig):
+        super().__init__()
+        if not cfg.obstacle_obs_dim > 0 or cfg.num_use_neighbor_obs < 1:
+            raise ValueError("encoder_type 'attention' needs obstacle observations and at least one neighbour "
+                             f"(obstacle_obs_dim {cfg.obstacle_obs_dim}, num_use_neighbor_obs {cfg.num_use_neighbor_obs})")
+        self.cfg = cfg
+        R = cfg.rnn_size
+        self.all_neighbor_obs_size = cfg.neighbor_obs_dim * cfg.num_use_neighbor_obs
+        self.self_embed_layer = _mlp(cfg, [cfg.self_obs_dim, R, R])
+        self.neighbor_embed_layer = _mlp(cfg, [self.all_neighbor_obs_size, R, R])
+        self.obstacle_embed_layer = _mlp(cfg, [cfg.obstacle_obs_dim, R, R])
+        self.attention_layer = MultiHeadAttention(self.N_HEAD, R, R, R)
+        self.feed_forward = nn.Sequential(nn.Linear(3 * R, 2 * R), nn.Tanh())
+        self.out_size = 2 * R
+
+    def tokens(self, obs):
+        """[B, 2 rnn_size]: the attention layer's two normalised tokens per agent, attn_embed.view(batch, -1) -- what
+        the fused rollout kernel computes (csrc/qs_policy_mha.h)."""
+        so, na = self.cfg.self_obs_dim, self.all_neighbor_obs_size
+        x = torch.stack((self.neighbor_embed_layer(obs[:, so:so + na]), self.obstacle_embed_layer(obs[:, so + na:])), dim=1)
+        return self.attention_layer(x)[0].reshape(obs.shape[0], -1)
+
+    def forward(self, obs, tokens=None):
+        """tokens: self.tokens(obs) computed elsewhere (policy_fused.FusedRolloutPolicy)."""
+        if tokens is None:
+            tokens = self.tokens(obs)
+        return self.feed_forward(torch.cat((self.self_embed_layer(obs[:, :self.cfg.self_obs_dim]), tokens), dim=1))
+
+
+def make_encoder(cfg: PolicyConfig):
+    """make_quadmulti_encoder (quad_multi_model.py:356-364), without its sim2real variant."""
+    if cfg.encoder_type == "attention":
+        return QuadMultiHeadAttentionEncoder(cfg)
+    if cfg.encoder_type != "mlp":
+        raise ValueError(f"encoder_type must be 'mlp' or 'attention', not {cfg.encoder_type!r}")
+    return QuadMultiEncoder(cfg)
+
+
 class SwarmActorCritic(nn.Module):
     """ActorCriticPolicyCustomSeparateWeights (ActorCriticPolicyCustom.py:294-577): separate actor and
     critic towers (encoder -> ModelCoreMLP [rnn_type 'full'] or identity -> MlpDecoder), action_net +
@@ -234,8 +304,8 @@ class SwarmActorCritic(nn.Module):
     def __init__(self, cfg: PolicyConfig):
         super().__init__()
         self.cfg = cfg
-        self.actor_encoder = QuadMultiEncoder(cfg)
-        self.critic_encoder = QuadMultiEncoder(cfg)
+        self.actor_encoder = make_encoder(cfg)
+        self.critic_encoder = make_encoder(cfg)
         full = cfg.rnn_type == "full" and cfg.rnn_num_layers > 0
         enc = self.actor_encoder.out_size
         core_sizes = [enc] + [cfg.rnn_size] * cfg.rnn_num_layers
@@ -543,7 +613,8 @@ class PPOTrainer:
             raise ValueError("update_precision must be 'fp32' or 'x3'")
         self.update_precision = update_precision
         self.fused_update = None
-        if update_precision == "x3":
+        # (the multi-head attention encoder has no backward kernel: its update is torch autograd at either setting)
+        if update_precision == "x3" and policy.cfg.encoder_type != "attention":
             if self.device.type != "cuda":
                 raise NAT.QuadSwarmError("update_precision='x3' needs a HIP device")
             from .encoder_train import FusedAttentionTrain

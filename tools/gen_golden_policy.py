@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Policy fixtures from the reference's own model code (TEST INFRASTRUCTURE, dev container only).
 
-    python tools/gen_golden_policy.py       # writes tests/golden/policy_<case>.npz + policy_<case>.json
+    python tools/gen_golden_policy.py [case ...]   # writes tests/golden/policy_<case>.npz + policy_<case>.json
 
 Builds the reference's `ActorCriticPolicyCustomSeparateWeights` (swarm_rl/models/ActorCriticPolicyCustom.py:284-554)
 with its `QuadMultiEncoder` / `QuadNeighborhoodEncoder{Attention,Deepsets,Mlp}` (swarm_rl/models/
@@ -219,13 +219,54 @@ def ref_cfg(fields):
     return types.SimpleNamespace(**c)
 
 
-def main():
+# The obstacle runs' encoder (encoder_type "attention": QuadMultiHeadAttentionEncoder, quad_multi_model.py:125-200), on
+# its own: floor repr 19 + pos_vel 6 x 2 + octomap SDF 9, rnn_size 128, batch 5
+MHA_CASE = (dict(obs_repr="xyz_vxyz_R_omega_floor", neighbor_obs_type="pos_vel", neighbor_visible_num=2, num_agents=8,
+                 neighbor_hidden_size=128, rnn_size=128, use_obstacles=True, obstacle_obs_type="octomap",
+                 encoder_type="attention", sim2real=False), 5)
+
+
+def mha_case():
+    """tests/golden/policy_mha.{json,npz}: observations and the reference encoder's fp64 output."""
+    from gym_art.quadrotor_multi.quad_utils import QUADS_NEIGHBOR_OBS_TYPE, QUADS_OBS_REPR, QUADS_OBSTACLE_OBS_TYPE
+    from swarm_rl.models.quad_multi_model import make_quadmulti_encoder
+
+    fields, B = MHA_CASE
+    cfg = ref_cfg(fields)
+    k, so, nd = cfg.neighbor_visible_num, QUADS_OBS_REPR[cfg.obs_repr], QUADS_NEIGHBOR_OBS_TYPE[cfg.neighbor_obs_type]
+    od = so + nd * k + QUADS_OBSTACLE_OBS_TYPE[cfg.obstacle_obs_type]
+    torch.manual_seed(0)
+    enc = make_quadmulti_encoder(cfg, None)
+    names, shapes = [], []
+    with torch.no_grad():
+        for n, p in enc.named_parameters():
+            p.copy_(param_value(n, p.shape, p.dtype))
+            names.append(n)
+            shapes.append(list(p.shape))
+    obs = np.random.default_rng(sum(map(ord, "mha"))).normal(0.0, 1.5, (B, od))
+    with torch.no_grad():
+        out = enc.double()({"obs": torch.from_numpy(obs)}).numpy()
+    np.savez_compressed(os.path.join(OUT, "policy_mha.npz"), obs=obs, features64=out)
+    meta = {"case": "mha", "ref_cfg": vars(cfg), "batch": B, "obs_dim": od, "self_obs_dim": so, "neighbor_obs_dim": nd,
+            "num_use_neighbor_obs": k, "obstacle_obs_dim": od - so - nd * k, "param_names": names,
+            "param_shapes": shapes, "param_count": int(sum(int(np.prod(s)) for s in shapes))}
+    with open(os.path.join(OUT, "policy_mha.json"), "w") as f:
+        json.dump(meta, f, indent=1)
+    print("mha", od, meta["param_count"], len(names))
+
+
+def main(only=()):
+    """only: the cases to (re)write (CASES' names, "mha"); all of them when empty."""
     install()
     from gymnasium import spaces
     from gym_art.quadrotor_multi.quad_utils import QUADS_NEIGHBOR_OBS_TYPE, QUADS_OBS_REPR, QUADS_OBSTACLE_OBS_TYPE
     from swarm_rl.models.ActorCriticPolicyCustom import ActorCriticPolicyCustomSeparateWeights
 
+    if not only or "mha" in only:
+        mha_case()
     for case, (fields, act_dim, B) in CASES.items():
+        if only and case not in only:
+            continue
         cfg = ref_cfg(fields)
         k = cfg.num_agents - 1 if cfg.neighbor_visible_num == -1 else cfg.neighbor_visible_num
         so = QUADS_OBS_REPR[cfg.obs_repr]
@@ -273,4 +314,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])
