@@ -697,6 +697,43 @@ typedef struct qs_mha_tower {
 int qs_mha_encoder_x3(const float* d_obs, int32_t obs_stride, int32_t self_dim, int32_t nbr_width, int32_t obst_dim,
                       int32_t B, int32_t H, const qs_mha_tower* towers, int32_t n_towers, void* stream);
 
+/* The PPO update's side of that encoder (csrc/qs_policy_mha_train.h): the forward with the activations its backward
+ * needs saved, and the backward's data gradient.  Per tower, all device memory; rows [B, 2, H] are agent-major (agent
+ * b's neighbour token, then its obstacle token).  w_*tp: the packed TRANSPOSES of the blocks qs_mha_tower packs (the
+ * backward's dX = G W operands; 4 blocks each for the attention weights, head h first). */
+#define QS_MHA_NCOLMAX 12
+typedef struct qs_mha_train {
+    float* x1;             /* [B, 2, H] saved: the embed layers' first tanh outputs                              */
+    float* x;              /* [B, 2, H] saved: the tokens (the embed layers' outputs)                            */
+    float* sm;             /* [B, 4, 2, 2] saved: softmax weights s[head][t][u]                                  */
+    float* xhat;           /* [B, 2, H] saved: the LayerNorm's normalised rows                                   */
+    float* rsig;           /* [B, 2] saved: 1 / sigma of each row                                                */
+    const float* dout;     /* [B, 2H] in (backward): dL / d out                                                  */
+    const void* w_fctp;    /* packed fc.weight[:, hH:(h+1)H]^T                                                   */
+    const void* w_qtp;     /* packed w_qs.weight[hH:(h+1)H, :]^T                                                 */
+    const void* w_ktp;     /* packed w_ks.weight[hH:(h+1)H, :]^T                                                 */
+    const void* w_vtp;     /* packed w_vs.weight[hH:(h+1)H, :]^T                                                 */
+    const void* w_n2tp;    /* packed neighbor_embed_layer[2].weight^T                                            */
+    const void* w_o2tp;    /* packed obstacle_embed_layer[2].weight^T                                            */
+    float* gmix;           /* [4, B, 2, H] out: G_h[u] = sum_t s_h[t][u] dy_t (dy: the gradient entering the LayerNorm) */
+    float* rmix;           /* [4, B, 2, H] out: R_h[t] = sum_u ds_h[t][u] x_u (ds: the gradient of q_t . k_u)    */
+    float* dpre2;          /* [B, 2, H] out: gradient of the embed layers' second pre-activations                */
+    float* dpre1;          /* [B, 2, H] out: gradient of their first pre-activations                             */
+    float* colmax;         /* [QS_MHA_NCOLMAX, ceil(B / 32), H] out: per-block column maxima of |.| (qs_colmax_reduce ->
+                              qs_dw_x3_ld's column scales): dpre2 token 0, token 1, dpre1 token 0, token 1, then G_h, R_h
+                              for h = 0 .. 3                                                                     */
+} qs_mha_train;
+/* qs_mha_encoder_x3 that also fills x1, x, sm, xhat, rsig of `trains`; towers[i].out is bitwise what
+ * qs_mha_encoder_x3 writes.  Arguments and ranges as qs_mha_encoder_x3. */
+int qs_mha_encoder_train_x3(const float* d_obs, int32_t obs_stride, int32_t self_dim, int32_t nbr_width, int32_t obst_dim,
+                            int32_t B, int32_t H, const qs_mha_tower* towers, const qs_mha_train* trains,
+                            int32_t n_towers, void* stream);
+/* From dout and the saved activations: the LayerNorm, attention (Q, K, V recomputed from x) and embed-layer backward
+ * of every 32-agent block; writes gmix, rmix, dpre2, dpre1 and colmax.  The weight gradients are products of those
+ * with x / x1 / the observations (qs_dw_x3_ld; quadswarm_amd.mha_train). */
+int qs_mha_bwd_x3(int32_t B, int32_t H, const qs_mha_tower* towers, const qs_mha_train* trains, int32_t n_towers,
+                  void* stream);
+
 /* sb_train's capture-radius curriculum on the device (ABI 11; replaces CurriculumCallback._on_step,
  * swarm_rl/custom_callbacks.py:441-468, which SB3 runs after every VecEnv step).  Flavor A.  The callback's state
  * is a qs_curriculum in DEVICE memory; qs_curriculum_step, enqueued after a qs_step, records the outcome of every

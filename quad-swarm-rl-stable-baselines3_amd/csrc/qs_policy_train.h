@@ -581,6 +581,9 @@ __global__ __launch_bounds__(NTHR, 2) void attn_bwd2_x3_kernel(int B, int K, Tow
 }  // namespace pol
 }  // namespace qs
 
+// (qs_policy_mha.hip includes this header for the staging helpers above only: the weight-gradient and statistics kernels
+// below, one of them not a template, are qs_policy_api.hip's)
+#ifndef QS_TRAIN_STAGING_ONLY
 namespace qs {
 namespace pol {
 
@@ -1151,3 +1154,4 @@ __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__
 
 }  // namespace pol
 }  // namespace qs
+#endif  // QS_TRAIN_STAGING_ONLY

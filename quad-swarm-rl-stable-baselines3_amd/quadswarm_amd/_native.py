@@ -174,6 +174,15 @@ class QsMhaTower(ctypes.Structure):
                                                 "w_vp", "w_fcp", "ln_g", "ln_b", "out")]
 
 
+MHA_NCOLMAX = 12          # qs_mha_train.colmax rows (QS_MHA_NCOLMAX)
+
+
+class QsMhaTrain(ctypes.Structure):
+    """qs_mha_train (the PPO update's saved activations and gradients of one multi-head attention tower, quadswarm.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("x1", "x", "sm", "xhat", "rsig", "dout", "w_fctp", "w_qtp", "w_ktp",
+                                                "w_vtp", "w_n2tp", "w_o2tp", "gmix", "rmix", "dpre2", "dpre1", "colmax")]
+
+
 class QsAttnTrain(ctypes.Structure):
     """qs_attn_train (the PPO update's saved activations and gradients of one tower, quadswarm.h)."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("e1", "a1", "a2", "v1", "h", "w", "dout", "dem", "w_v2tp", "w_v1tp",
@@ -216,7 +225,7 @@ EXPORTS = ["qs_abi_version", "qs_last_error", "qs_struct_sizes", "qs_config_defa
            "qs_attn_bwd1_x3", "qs_attn_bwd2_x3", "qs_attn_dw_x3", "qs_attn_dw0_x3", "qs_colmax_reduce", "qs_colstats",
            "qs_linear_tanh_x3", "qs_dw_x3_ld", "qs_linear_rows_x3",
            "qs_tanh_grad_stats", "qs_linear_bias_x3", "qs_slab_sum_stats",
-           "qs_linear_tanh_cat_x3", "qs_mha_encoder_x3"]
+           "qs_linear_tanh_cat_x3", "qs_mha_encoder_x3", "qs_mha_encoder_train_x3", "qs_mha_bwd_x3"]
 EXPORTS += ["qs_render_config_default", "qs_render_query", "qs_render"]
 EXPORTS += ["qs_shaping_config_default", "qs_shaping_workspace_bytes", "qs_shaping_enable", "qs_shaping_disable",
             "qs_shaping_buffers_get", "qs_shaping_set_training_steps"]
@@ -277,6 +286,8 @@ def lib():
         "qs_slab_sum_stats": ([V, I32, ctypes.c_int64, I32, V, V, V, V], I32),
         "qs_linear_tanh_cat_x3": ([V, V, ctypes.c_int64, V, ctypes.c_int64, V, V, I32, V], I32),
         "qs_mha_encoder_x3": ([V, I32, I32, I32, I32, I32, I32, P(QsMhaTower), I32, V], I32),
+        "qs_mha_encoder_train_x3": ([V, I32, I32, I32, I32, I32, I32, P(QsMhaTower), P(QsMhaTrain), I32, V], I32),
+        "qs_mha_bwd_x3": ([I32, I32, P(QsMhaTower), P(QsMhaTrain), I32, V], I32),
     }
     sig.update({
         "qs_render_config_default": ([P(QsRenderConfig)], I32),

@@ -189,6 +189,49 @@ def supports(policy):
             c.num_use_neighbor_obs <= 64 and c.self_obs_dim + c.neighbor_obs_dim <= 32 and c.nonlinearity == "tanh")
 
 
+def mha_weight_range(encs):
+    """(max |w| over the multi-head attention encoders' matrices the kernels pack, max_row |w_vs|_1): the two numbers the
+    split-f16 range rules bound (|w| < 255.9; |ctx| <= max_row |w_vs|_1 < 65504 / X3_SC).  One host read."""
+    stats = []
+    for enc in encs:
+        at = enc.attention_layer
+        ms = (enc.neighbor_embed_layer[0], enc.neighbor_embed_layer[2], enc.obstacle_embed_layer[0],
+              enc.obstacle_embed_layer[2], at.w_qs, at.w_ks, at.w_vs, at.fc)
+        stats.append(torch.stack((torch.stack([m.weight.detach().abs().amax() for m in ms]).amax(),
+                                  at.w_vs.weight.detach().abs().sum(dim=1).amax())))
+    return torch.stack(stats).amax(dim=0).tolist()
+
+
+def mha_range_ok(big, vnorm):
+    return big < F16_MAX / X3_SW and vnorm < F16_MAX / X3_SC   # NaN fails too
+
+
+def pack_mha_tower(enc, H, nbw, od, transposes=False):
+    """One tower's qs_mha_tower operands (quadswarm.h): the packed weights and the bias / LayerNorm vectors.
+    transposes: also the backward's W^T operands (qs_mha_train w_*tp), packed in the same batch."""
+    ne, oe, at = enc.neighbor_embed_layer, enc.obstacle_embed_layer, enc.attention_layer
+    w_e1 = torch.zeros(H, MHA_NBW + MHA_OBW, dtype=torch.float32, device=ne[0].weight.device)
+    w_e1[:, :nbw] = ne[0].weight.detach()                       # [neighbour block | 0 | obstacle values | 0]
+    w_e1[:, MHA_NBW:MHA_NBW + od] = oe[0].weight.detach()
+    rows = lambda lin: [lin.weight[h * H:(h + 1) * H] for h in range(4)]  # noqa: E731  head h's projection
+    fcs = [at.fc.weight[:, h * H:(h + 1) * H] for h in range(4)]
+    mats = [w_e1, ne[2].weight, oe[2].weight] + rows(at.w_qs) + rows(at.w_ks) + rows(at.w_vs) + fcs   # 18 [H, H]: one batch
+    if transposes:
+        mats += [m.t() for m in mats[1:]]
+    pk = pack_mfma_weights_x3(mats)
+    w = dict(w_e1p=pk[0], w_n2p=pk[1], w_o2p=pk[2], w_qp=torch.stack(pk[3:7]), w_kp=torch.stack(pk[7:11]),
+             w_vp=torch.stack(pk[11:15]), w_fcp=torch.stack(pk[15:19]),
+             b_n1=ne[0].bias.detach(), b_o1=oe[0].bias.detach(), b_n2=ne[2].bias.detach(),
+             b_o2=oe[2].bias.detach(), ln_g=at.layer_norm.weight.detach(), ln_b=at.layer_norm.bias.detach())
+    if transposes:
+        w.update(w_n2tp=pk[19], w_o2tp=pk[20], w_qtp=torch.stack(pk[21:25]), w_ktp=torch.stack(pk[25:29]),
+                 w_vtp=torch.stack(pk[29:33]), w_fctp=torch.stack(pk[33:37]))
+    return w
+
+
+MHA_TOWER_FIELDS = ("w_e1p", "b_n1", "b_o1", "w_n2p", "w_o2p", "b_n2", "b_o2", "w_qp", "w_kp", "w_vp", "w_fcp", "ln_g", "ln_b")
+
+
 class FusedRolloutPolicy:
     """forward(obs) / predict_values(obs) of a SwarmActorCritic with the fused neighbour encoders.
     refresh() re-packs the weights: call it whenever the policy's parameters changed (PPOTrainer does,
@@ -314,15 +357,8 @@ class FusedRolloutPolicy:
         prec = "torch"
         if self.precision == "x3":
             prec = "x3"
-            stats = []
-            for enc in self.encs:
-                at = enc.attention_layer
-                ms = (enc.neighbor_embed_layer[0], enc.neighbor_embed_layer[2], enc.obstacle_embed_layer[0],
-                      enc.obstacle_embed_layer[2], at.w_qs, at.w_ks, at.w_vs, at.fc)
-                stats.append(torch.stack((torch.stack([m.weight.detach().abs().amax() for m in ms]).amax(),
-                                          at.w_vs.weight.detach().abs().sum(dim=1).amax())))
-            big, vnorm = torch.stack(stats).amax(dim=0).tolist()   # one host read
-            if not (big < F16_MAX / X3_SW and vnorm < F16_MAX / X3_SC):   # NaN fails too
+            big, vnorm = mha_weight_range(self.encs)
+            if not mha_range_ok(big, vnorm):
                 import warnings
                 warnings.warn(f"x3 rollout encoders: max |w| = {big:.4g} (limit {F16_MAX / X3_SW:.4g}), max row |w_vs|_1 = "
                               f"{vnorm:.4g} (limit {F16_MAX / X3_SC:.4g}): outside the split-f16 range; evaluating in torch")
@@ -334,17 +370,7 @@ class FusedRolloutPolicy:
         H, nbw, od = self.H, self.nd * self.K, self.cfg.obstacle_obs_dim
         packed = []
         for enc in self.encs:
-            ne, oe, at = enc.neighbor_embed_layer, enc.obstacle_embed_layer, enc.attention_layer
-            w_e1 = torch.zeros(H, MHA_NBW + MHA_OBW, dtype=torch.float32, device=ne[0].weight.device)
-            w_e1[:, :nbw] = ne[0].weight.detach()                       # [neighbour block | 0 | obstacle values | 0]
-            w_e1[:, MHA_NBW:MHA_NBW + od] = oe[0].weight.detach()
-            rows = lambda lin: [lin.weight[h * H:(h + 1) * H] for h in range(4)]  # noqa: E731  head h's projection
-            pk = pack_mfma_weights_x3([w_e1, ne[2].weight, oe[2].weight] + rows(at.w_qs) + rows(at.w_ks) + rows(at.w_vs)
-                                      + [at.fc.weight[:, h * H:(h + 1) * H] for h in range(4)])   # 18 [H, H]: one batch
-            w = dict(w_e1p=pk[0], w_n2p=pk[1], w_o2p=pk[2], w_qp=torch.stack(pk[3:7]), w_kp=torch.stack(pk[7:11]),
-                     w_vp=torch.stack(pk[11:15]), w_fcp=torch.stack(pk[15:19]),
-                     b_n1=ne[0].bias.detach(), b_o1=oe[0].bias.detach(), b_n2=ne[2].bias.detach(),
-                     b_o2=oe[2].bias.detach(), ln_g=at.layer_norm.weight.detach(), ln_b=at.layer_norm.bias.detach())
+            w = pack_mha_tower(enc, H, nbw, od)
             se = enc.self_embed_layer
             if self_l2_supported(se) and float(se[2].weight.detach().abs().amax()) < F16_MAX / X3_SW:
                 w.update(w_s2p=pack_linear_x3(se[2].weight.detach()), b_s2=se[2].bias.detach().contiguous())
@@ -357,8 +383,7 @@ class FusedRolloutPolicy:
             return
         for i, w in enumerate(self.packed):
             t = self.towers[i]
-            for name in ("w_e1p", "b_n1", "b_o1", "w_n2p", "w_o2p", "b_n2", "b_o2", "w_qp", "w_kp", "w_vp", "w_fcp",
-                         "ln_g", "ln_b"):
+            for name in MHA_TOWER_FIELDS:
                 assert w[name].is_contiguous()
                 setattr(t, name, w[name].data_ptr())
             t.out = self.out[i].data_ptr()

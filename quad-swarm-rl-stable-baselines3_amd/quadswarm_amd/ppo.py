@@ -341,16 +341,19 @@ class SwarmActorCritic(nn.Module):
 
     def evaluate_actions(self, obs, actions, nbr=None, l0=None, ff=None):
         """(values, log_prob, entropy=None) -- ActorCriticPolicyCustom.py:538-566.  nbr: (actor, critic) neighbour
-        encoder outputs from the fused update (encoder_train.FusedAttentionTrain), else the torch encoders run;
+        encoder outputs from the fused update (encoder_train.FusedAttentionTrain; for the multi-head attention encoder
+        its two towers' tokens, mha_train.FusedMhaTrain), else the torch encoders run;
         l0 / ff: the fused update's self-encoder first layer and feed_forward (FusedAttentionTrain.self_layer0 /
         .feed_forward), with nbr only."""
         if nbr is None:
             mean = self.action_net(self.actor_latent(obs))
             return self.predict_values(obs), squashed_log_prob(mean, self.log_std, actions), None
-        mean = head_linear(self.action_net,
-                           self.actor_decoder(self.actor_core(self.actor_encoder(obs, nbr[0], l0, ff))))
-        values = head_linear(self.value_net,
-                             self.critic_decoder(self.critic_core(self.critic_encoder(obs, nbr[1], l0, ff))))
+        if self.cfg.encoder_type == "attention":   # nbr: the two towers' attention tokens (mha_train.FusedMhaTrain)
+            enc = lambda e, tok: e(obs, tokens=tok)  # noqa: E731
+        else:
+            enc = lambda e, out: e(obs, out, l0, ff)  # noqa: E731
+        mean = head_linear(self.action_net, self.actor_decoder(self.actor_core(enc(self.actor_encoder, nbr[0]))))
+        values = head_linear(self.value_net, self.critic_decoder(self.critic_core(enc(self.critic_encoder, nbr[1]))))
         return values, squashed_log_prob(mean, self.log_std, actions), None
 
     def predict(self, obs, deterministic=True):
@@ -569,7 +572,8 @@ class PPOTrainer:
     the trainer on a CPU stand-in env; the default is the HIP kernel."""
 
     def __init__(self, env, policy: SwarmActorCritic, cfg: PPOConfig = None, device=None, seed=0,
-                 gae_fn=None, group=None, fused_rollout=True, rollout_precision="fp32", update_precision="fp32"):
+                 gae_fn=None, group=None, fused_rollout=True, rollout_precision="fp32", update_precision="fp32",
+                 mha_update="torch"):
         import torch.distributed as dist
 
         self.env, self.policy, self.cfg = env, policy, cfg or PPOConfig()
@@ -613,12 +617,22 @@ class PPOTrainer:
             raise ValueError("update_precision must be 'fp32' or 'x3'")
         self.update_precision = update_precision
         self.fused_update = None
-        # (the multi-head attention encoder has no backward kernel: its update is torch autograd at either setting)
         if update_precision == "x3" and policy.cfg.encoder_type != "attention":
             if self.device.type != "cuda":
                 raise NAT.QuadSwarmError("update_precision='x3' needs a HIP device")
             from .encoder_train import FusedAttentionTrain
             self.fused_update = FusedAttentionTrain(policy)
+        # the multi-head attention encoder's update: torch autograd ("torch") or its tokens' forward and backward on
+        # the fused split-f16 kernels ("x3", mha_train.py); its own switch, update_precision does not reach this family
+        if mha_update not in ("torch", "x3"):
+            raise ValueError("mha_update must be 'torch' or 'x3'")
+        self.mha_update = mha_update
+        self.fused_mha = None
+        if mha_update == "x3" and policy.cfg.encoder_type == "attention":
+            if self.device.type != "cuda":
+                raise NAT.QuadSwarmError("mha_update='x3' needs a HIP device")
+            from .mha_train import FusedMhaTrain
+            self.fused_mha = FusedMhaTrain(policy)
 
     def reset(self):
         self.last_obs = self.env.reset()
@@ -717,15 +731,18 @@ class PPOTrainer:
         # the fused x3 encoders only where the rollout's observations are inside their split-f16 range (one check per
         # update, whatever the rollout's precision); a weight out of range falls back per minibatch (encodings -> None)
         fused = self.fused_update if self.fused_update is not None and self.fused_update.obs_in_range(obs) else None
+        fused_mha = self.fused_mha if self.fused_mha is not None and self.fused_mha.obs_in_range(obs) else None
         for _ in range(c.n_epochs):
             perm = torch.randperm(n, device=self.device, generator=self.gen)
             for s in range(0, n, c.batch_size):
                 idx = perm[s:s + c.batch_size]
                 ob = obs[idx]
                 nbr = fused.encodings(ob) if fused is not None else None
+                if fused_mha is not None:
+                    nbr = fused_mha.tokens(ob)   # None: a weight out of range, this minibatch on torch autograd
                 values, logp, entropy = pol.evaluate_actions(ob, act[idx], nbr=nbr,
-                                                             l0=fused.self_layer0 if nbr is not None else None,
-                                                             ff=fused.feed_forward if nbr is not None else None)
+                                                             l0=fused.self_layer0 if fused and nbr is not None else None,
+                                                             ff=fused.feed_forward if fused and nbr is not None else None)
                 values = values.flatten()
                 adv = adv_all[idx]
                 if c.normalize_advantage and idx.numel() > 1:
