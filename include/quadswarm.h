@@ -734,6 +734,34 @@ int qs_mha_encoder_train_x3(const float* d_obs, int32_t obs_stride, int32_t self
 int qs_mha_bwd_x3(int32_t B, int32_t H, const qs_mha_tower* towers, const qs_mha_train* trains, int32_t n_towers,
                   void* stream);
 
+/* The rollout policy's tail as one launch (csrc/qs_policy_tail.h): per tower, from the encoder's feed_forward output
+ * X [B, 2R] (fp32, |x| <= 1: tanh outputs) through a chain of n_layers (0 .. QS_TAIL_MAX_LAYERS) Linear + tanh layers
+ * (ModelCoreMLP's, then the MlpDecoder's; layer 0 is [R, 2R], the others [R, R]; R 128 or 256) on the split-f16 matrix
+ * cores, then the head Linear [n_out <= QS_TAIL_MAX_OUT, Win] in fp32 (Win = R, or 2R when n_layers is 0) and
+ *   actor  (log_std != NULL): u = mean + exp(log_std) eps (u = mean when deterministic or eps is NULL), out = a =
+ *          tanh(u), log_prob = SquashedDiagGaussianDistribution.log_prob of the stored a (clamped to +-(1 - 2^-23),
+ *          atanh by log1p, minus sum log(1 - a^2 + 1e-6));
+ *   critic (log_std == NULL): out = the head's outputs (value_net: n_out 1).
+ * No intermediate activation is written to memory.  Up to QS_ATTN_MAX_TOWERS towers per launch (they share B, R and
+ * n_layers); a critic tower alone is valid.  w_chain[l]: packed as for qs_attn_embed_x3
+ * (quadswarm_amd.policy_fused.pack_mfma_weight_x3; |w| < 255.9, the caller checks).  Asynchronous on `stream`. */
+#define QS_TAIL_MAX_LAYERS 8
+#define QS_TAIL_MAX_OUT 8
+typedef struct qs_tail_tower {
+    const float* x;                             /* [B, 2R] in */
+    const void* w_chain[QS_TAIL_MAX_LAYERS];    /* packed chain weights (the first n_layers) */
+    const float* b_chain[QS_TAIL_MAX_LAYERS];   /* [R] each */
+    const float* w_head;                        /* [n_out, Win] fp32, row-major */
+    const float* b_head;                        /* [n_out] */
+    const float* log_std;                       /* [n_out], or NULL: critic */
+    const float* eps;                           /* [B, n_out] standard normal draws, or NULL */
+    float* out;                                 /* [B, n_out] out: actions (actor) or head outputs (critic) */
+    float* log_prob;                            /* [B] out (actor) */
+    int32_t n_out;
+    int32_t deterministic;
+} qs_tail_tower;
+int qs_policy_tail_x3(int64_t B, int32_t R, int32_t n_layers, const qs_tail_tower* towers, int32_t n_towers, void* stream);
+
 /* sb_train's capture-radius curriculum on the device (ABI 11; replaces CurriculumCallback._on_step,
  * swarm_rl/custom_callbacks.py:441-468, which SB3 runs after every VecEnv step).  Flavor A.  The callback's state
  * is a qs_curriculum in DEVICE memory; qs_curriculum_step, enqueued after a qs_step, records the outcome of every

@@ -8,7 +8,7 @@ Per step, for the actor and the critic tower at once (one launch per stage):
   HIP     e1 (self and neighbour halves of layer 0), e2 rows, mean_K(e2)   (qs_attn_embed)
   HIP     P = mean_K(e2) W_a1[:, H:]^T + b_a1 (x3, H 256; else torch)   [B, H]
   HIP     value path, attention path, softmax over K, pooled out    (qs_attn_pool)
-  torch   self encoder, feed_forward, core, decoder, heads          (small per-agent GEMMs)
+  torch   self encoder, feed_forward, core, decoder, heads          (small per-agent GEMMs; tail="x3": below)
 The result is the same function as the torch module (fp32 throughout; only the summation order of the
 GEMMs differs: tests/test_gpu_policy_fused.py bounds it).  Training (the PPO update with autograd) keeps
 the torch module.
@@ -17,6 +17,10 @@ A policy built with encoder_type "attention" (the obstacle runs' QuadMultiHeadAt
 125-200) is the second family: with precision "x3" one launch of qs_mha_encoder_x3 (csrc/qs_policy_mha.h) takes both
 towers from the observations to the two normalised attention tokens per agent; the self encoder and feed_forward
 stay in torch (the self encoder's second layer on qs_linear_tanh_x3 where it fits).  tests/test_gpu_policy_mha.py.
+
+tail="x3" (either family): everything after the feed_forward -- core, decoder, action_net / value_net, the squashed
+Gaussian's sampling and log-prob -- is one launch of qs_policy_tail_x3 (csrc/qs_policy_tail.h) for both towers in place
+of the torch row above.  tests/test_gpu_policy_tail.py.
 """
 import ctypes
 
@@ -189,6 +193,22 @@ def supports(policy):
             c.num_use_neighbor_obs <= 64 and c.self_obs_dim + c.neighbor_obs_dim <= 32 and c.nonlinearity == "tanh")
 
 
+def tail_chain(core, decoder):
+    """The Linear layers of a tower's core followed by its decoder's: the chain qs_policy_tail_x3 evaluates."""
+    return [m for m in list(core) + list(decoder) if isinstance(m, torch.nn.Linear)]
+
+
+def tail_supports(policy):
+    """Can qs_policy_tail_x3 evaluate this policy's core, decoder, heads and action distribution?  tanh layers, all
+    of width rnn_size (128 or 256) after the 2 rnn_size wide feed_forward, at most 8 of them, act_dim <= 8."""
+    c = policy.cfg
+    full = c.rnn_type == "full" and c.rnn_num_layers > 0
+    n = (c.rnn_num_layers if full else 0) + len(c.decoder_mlp_layers)
+    return (c.nonlinearity == "tanh" and c.rnn_size in (128, 256) and n <= NAT.TAIL_MAX_LAYERS and
+            all(d == c.rnn_size for d in c.decoder_mlp_layers) and 1 <= c.act_dim <= NAT.TAIL_MAX_OUT and
+            policy.actor_encoder.out_size == 2 * c.rnn_size)
+
+
 def mha_weight_range(encs):
     """(max |w| over the multi-head attention encoders' matrices the kernels pack, max_row |w_vs|_1): the two numbers the
     split-f16 range rules bound (|w| < 255.9; |ctx| <= max_row |w_vs|_1 < 65504 / X3_SC).  One host read."""
@@ -238,13 +258,24 @@ class FusedRolloutPolicy:
     once per rollout)."""
 
     PRECISIONS = ("fp32", "x3")
+    TAILS = ("torch", "x3")
 
-    def __init__(self, policy, precision="fp32"):
+    def __init__(self, policy, precision="fp32", tail="torch"):
         """precision "fp32": fp32 operands on the fp32 matrix cores (v_mfma_f32_32x32x2f32); "x3": every fp32 product
         as three f16 products (hi/lo split, fp32 accumulation, ~7e-7 relative per product) on the f16 matrix cores
-        (csrc/qs_policy_x3.h), 5.3x the contraction rate."""
+        (csrc/qs_policy_x3.h), 5.3x the contraction rate.
+        tail "torch": core, decoder, heads and the action distribution as torch launches; "x3": as one launch of
+        qs_policy_tail_x3 (csrc/qs_policy_tail.h; the chain's products split like precision "x3", the heads fp32)."""
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision must be one of {self.PRECISIONS}")
+        if tail not in self.TAILS:
+            raise ValueError(f"tail must be one of {self.TAILS}")
+        if tail == "x3" and not tail_supports(policy):
+            raise ValueError("fused rollout tail: needs tanh core / decoder layers of width rnn_size (128 or 256), at "
+                             "most 8 of them, and act_dim <= 8")
+        self.tail_mode = tail
+        self.packed_tail = None        # what refresh() packed for the x3 tail; None: the torch tail evaluates
+        self.tail_towers = (NAT.QsTailTower * NAT.ATTN_MAX_TOWERS)()
         self.precision = precision
         self.packed_precision = None   # what refresh() packed: precision, or fp32 when x3 weights are out of range
         self._obs_absmax = None        # running max |obs| the x3 layer 0 has seen since the last check_inputs()
@@ -268,6 +299,8 @@ class FusedRolloutPolicy:
     def refresh(self):
         """Re-pack the weights.  x3: a weight outside the split-f16 range (|w| >= 255.9) would become +-inf; the
         towers are then packed (and evaluated) in fp32 until a later refresh finds every weight in range again."""
+        if self.tail_mode == "x3":
+            self._refresh_tail()
         if self.mha:
             return self._refresh_mha()
         prec = self.precision
@@ -413,6 +446,86 @@ class FusedRolloutPolicy:
             s = se(obs[:, :self.so])
         return enc.feed_forward(torch.cat((s, tokens), dim=1))
 
+    # ---- the tail: core, decoder, heads, action distribution ----
+    def _refresh_tail(self):
+        """Pack both towers' chains for qs_policy_tail_x3.  A chain weight outside the split-f16 range (|w| >= 255.9)
+        would become +-inf: the torch tail then evaluates until a later refresh finds every weight in range again."""
+        pol = self.policy
+        chains = (tail_chain(pol.actor_core, pol.actor_decoder), tail_chain(pol.critic_core, pol.critic_decoder))
+        heads = (pol.action_net, pol.value_net)
+        self.packed_tail = None
+        mats = [m.weight for ch in chains for m in ch]
+        if mats:
+            lim = F16_MAX / X3_SW
+            big = float(torch.stack([w.detach().abs().amax() for w in mats]).amax())
+            if not big < lim:
+                import warnings
+                warnings.warn(f"x3 rollout tail: max |w| = {big:.4g} >= {lim:.4g} (f16 range); evaluating in torch")
+                return
+        pk = pack_mfma_weights_x3(mats) if mats else []
+        n = len(chains[0])
+        keep = []   # the tensors the towers point into
+        for i, (ch, head) in enumerate(zip(chains, heads)):
+            t = self.tail_towers[i]
+            for l, m in enumerate(ch):
+                w, b = pk[i * n + l].contiguous(), m.bias.detach().contiguous()
+                t.w_chain[l], t.b_chain[l] = w.data_ptr(), b.data_ptr()
+                keep += [w, b]
+            w, b = head.weight.detach().contiguous(), head.bias.detach().contiguous()
+            assert w.shape == (head.out_features, self.cfg.rnn_size if n else 2 * self.cfg.rnn_size)
+            t.w_head, t.b_head, t.n_out = w.data_ptr(), b.data_ptr(), head.out_features
+            keep += [w, b]
+        ls = pol.log_std.detach().contiguous()
+        self.tail_towers[0].log_std = ls.data_ptr()
+        self.tail_towers[1].log_std = None
+        self.packed_tail = dict(n_layers=n, keep=keep + [ls])
+
+    @torch.no_grad()
+    def tail(self, latents_actor, latents_critic, noise=None, deterministic=False):
+        """(actions, values [B, 1], log_prob [B]) from the towers' feed_forward outputs [B, 2 rnn_size]: core, decoder,
+        action_net / value_net, actions = tanh(mean + exp(log_std) noise) (tanh(mean) when deterministic or without
+        noise [B, act_dim]) and their squashed-Gaussian log-prob.  latents_actor None: the critic alone, (None, values,
+        None).  tail "x3": one launch of qs_policy_tail_x3, unless refresh() found a chain weight out of range."""
+        pol = self.policy
+        if self.tail_mode == "x3" and self.packed is None:
+            self.refresh()
+        if self.tail_mode != "x3" or self.packed_tail is None:
+            from .ppo import squashed_log_prob
+            values = pol.value_net(pol.critic_decoder(pol.critic_core(latents_critic)))
+            if latents_actor is None:
+                return None, values, None
+            mean = pol.action_net(pol.actor_decoder(pol.actor_core(latents_actor)))
+            sample = noise is not None and not deterministic
+            actions = torch.tanh(mean + noise * pol.log_std.exp()) if sample else torch.tanh(mean)
+            return actions, values, squashed_log_prob(mean, pol.log_std, actions)
+        R, dev = self.cfg.rnn_size, latents_critic.device
+        B = latents_critic.shape[0]
+        lats = [x for x in (latents_actor, latents_critic) if x is not None]
+        assert all(x.is_cuda and x.dtype == torch.float32 and x.shape == (B, 2 * R) for x in lats)
+        lats = [x.contiguous() for x in lats]
+        values = torch.empty(B, 1, dtype=torch.float32, device=dev)
+        actions = log_prob = None
+        tc = self.tail_towers[1]
+        tc.x, tc.out = lats[-1].data_ptr(), values.data_ptr()
+        towers, n_towers = self.tail_towers, 2
+        if latents_actor is None:
+            towers, n_towers = ctypes.pointer(tc), 1
+        else:
+            actions = torch.empty(B, self.cfg.act_dim, dtype=torch.float32, device=dev)
+            log_prob = torch.empty(B, dtype=torch.float32, device=dev)
+            ta = self.tail_towers[0]
+            if noise is not None and not deterministic:
+                assert noise.is_cuda and noise.dtype == torch.float32 and noise.shape == actions.shape
+                noise = noise.contiguous()
+                ta.eps = noise.data_ptr()
+            else:
+                ta.eps = None
+            ta.deterministic = int(bool(deterministic))
+            ta.x, ta.out, ta.log_prob = lats[0].data_ptr(), actions.data_ptr(), log_prob.data_ptr()
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        NAT.check(self.L.qs_policy_tail_x3(B, R, self.packed_tail["n_layers"], towers, n_towers, st), "qs_policy_tail_x3")
+        return actions, values, log_prob
+
     # ---- forward ----
     @torch.no_grad()
     def neighbor_encodings(self, obs):
@@ -467,6 +580,11 @@ class FusedRolloutPolicy:
         from .ppo import squashed_log_prob
         pol = self.policy
         nbr = self.neighbor_encodings(obs)
+        if self.tail_mode == "x3":
+            lat = [self._encode(enc, obs, nbr[i], self.packed[i]) for i, enc in enumerate(self.encs)]
+            # (the draw of randn_like(mean) below: same generator, same shape)
+            noise = None if deterministic else torch.randn((obs.shape[0], self.cfg.act_dim), device=obs.device)
+            return self.tail(lat[0], lat[1], noise, deterministic)
         a_lat = pol.actor_decoder(pol.actor_core(self._encode(pol.actor_encoder, obs, nbr[0], self.packed[0])))
         mean = pol.action_net(a_lat)
         values = pol.value_net(pol.critic_decoder(pol.critic_core(self._encode(pol.critic_encoder, obs, nbr[1],
@@ -483,5 +601,7 @@ class FusedRolloutPolicy:
     def predict_values(self, obs):
         pol = self.policy
         nbr = self.neighbor_encodings(obs)
+        if self.tail_mode == "x3":
+            return self.tail(None, self._encode(pol.critic_encoder, obs, nbr[1], self.packed[1]))[1]
         return pol.value_net(pol.critic_decoder(pol.critic_core(self._encode(pol.critic_encoder, obs, nbr[1],
                                                                              self.packed[1]))))

@@ -573,8 +573,11 @@ class PPOTrainer:
 
     def __init__(self, env, policy: SwarmActorCritic, cfg: PPOConfig = None, device=None, seed=0,
                  gae_fn=None, group=None, fused_rollout=True, rollout_precision="fp32", update_precision="fp32",
-                 mha_update="torch"):
+                 mha_update="torch", rollout_tail="torch"):
         import torch.distributed as dist
+
+        if rollout_tail not in ("torch", "x3"):
+            raise ValueError("rollout_tail must be 'torch' or 'x3'")
 
         self.env, self.policy, self.cfg = env, policy, cfg or PPOConfig()
         self.device = torch.device(device) if device is not None else next(policy.parameters()).device
@@ -606,11 +609,17 @@ class PPOTrainer:
         self._shaping_seen = None
         # the rollout's policy evaluations through the fused HIP attention encoders (policy_fused.py) where
         # the policy has that encoder; the update keeps the torch module (autograd)
+        # rollout_tail "x3": what follows the encoders too (core, decoder, heads, sampling, log-prob) as one launch of
+        # qs_policy_tail_x3 per evaluation instead of torch launches
         self.fused = None
+        if rollout_tail == "x3" and self.device.type != "cuda":
+            raise NAT.QuadSwarmError("rollout_tail='x3' needs a HIP device")
         if fused_rollout and self.device.type == "cuda":
             from .policy_fused import FusedRolloutPolicy, supports
             if supports(policy):
-                self.fused = FusedRolloutPolicy(policy, precision=rollout_precision)
+                self.fused = FusedRolloutPolicy(policy, precision=rollout_precision, tail=rollout_tail)
+        if rollout_tail == "x3" and self.fused is None:
+            raise ValueError("rollout_tail='x3' needs the fused rollout (fused_rollout=True and a policy it supports)")
         # the update's neighbour encoders: torch autograd ("fp32") or the fused split-f16 kernels ("x3",
         # encoder_train.py: forward + backward on the matrix cores, fp32-equivalent products)
         if update_precision not in ("fp32", "x3"):
