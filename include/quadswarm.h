@@ -762,6 +762,36 @@ typedef struct qs_tail_tower {
 } qs_tail_tower;
 int qs_policy_tail_x3(int64_t B, int32_t R, int32_t n_layers, const qs_tail_tower* towers, int32_t n_towers, void* stream);
 
+/* The PPO update's policy tail (csrc/qs_policy_tail_train.h; new symbols, the ABI version is unchanged): what one
+ * tower's forward saves and its backward reads and writes.  Every array is the caller's device memory. */
+typedef struct qs_tail_train {
+    float* y[QS_TAIL_MAX_LAYERS];               /* [B, R] each: chain layer l's tanh output (forward out, backward in) */
+    float* mean;                                /* [B, n_out] actor: the head's outputs (forward out, backward in) */
+    const float* actions;                       /* [B, n_out] actor: the stored actions */
+    const float* dvalues;                       /* [B, n_out] critic: gradient of the head's outputs (backward in) */
+    const float* dlogp;                         /* [B] actor: gradient of log_prob (backward in) */
+    float* dpre[QS_TAIL_MAX_LAYERS];            /* [B, R] each, backward out: gradient of layer l's pre-activations */
+    float* dlat;                                /* [B, 2R] backward out: gradient of x */
+    float* colmax;                              /* [n_layers, grid_x, R] backward out: per-block column maxima of |dpre_l|
+                                                   (qs_colmax_reduce -> qs_dw_x3_ld's column scales); +inf: non-finite */
+    float* head_part;                           /* [grid_x, n_out, Win + 1] backward out: per-block parts of the head's
+                                                   weight gradient, the bias gradient in the last column */
+    float* log_std_part;                        /* [grid_x, n_out] backward out (actor): per-block parts of log_std's */
+    const void* w_chain_t[QS_TAIL_MAX_LAYERS];  /* packed W_l^T ([R, R]; layer 0: the two blocks W_0[:, :R]^T and
+                                                   W_0[:, R:]^T, contiguous) */
+} qs_tail_train;
+/* qs_policy_tail_x3's chain and head with every layer's output saved in trains[i].y; the actor takes trains[i].actions
+ * in place of noise and writes trains[i].mean and towers[i].log_prob (of those actions; towers[i].out, eps and
+ * deterministic are not used), the critic towers[i].out.  The critic's out and the actor's log_prob of the actions
+ * qs_policy_tail_x3 stored are bitwise that kernel's. */
+int qs_policy_tail_train_x3(int64_t B, int32_t R, int32_t n_layers, const qs_tail_tower* towers, const qs_tail_train* trains,
+                            int32_t n_towers, void* stream);
+/* From dvalues / dlogp and the saves: dpre, dlat, colmax and the head / log_std gradient parts, by grid_x blocks per
+ * tower (1 .. ceil(B / 64)) that each walk the 64-row tiles grid_x apart.  The chain's weight gradients are dpre_l^T
+ * y_{l-1} (qs_dw_x3_ld; quadswarm_amd.tail_train). */
+int qs_policy_tail_bwd_x3(int64_t B, int32_t R, int32_t n_layers, const qs_tail_tower* towers, const qs_tail_train* trains,
+                          int32_t n_towers, int32_t grid_x, void* stream);
+
 /* sb_train's capture-radius curriculum on the device (ABI 11; replaces CurriculumCallback._on_step,
  * swarm_rl/custom_callbacks.py:441-468, which SB3 runs after every VecEnv step).  Flavor A.  The callback's state
  * is a qs_curriculum in DEVICE memory; qs_curriculum_step, enqueued after a qs_step, records the outcome of every

@@ -186,6 +186,15 @@ class QsTailTower(ctypes.Structure):
                [("n_out", ctypes.c_int32), ("deterministic", ctypes.c_int32)]
 
 
+class QsTailTrain(ctypes.Structure):
+    """qs_tail_train (the PPO update's saves and gradients of one tower's tail, quadswarm.h)."""
+    _fields_ = [("y", ctypes.c_void_p * TAIL_MAX_LAYERS)] + \
+               [(n, ctypes.c_void_p) for n in ("mean", "actions", "dvalues", "dlogp")] + \
+               [("dpre", ctypes.c_void_p * TAIL_MAX_LAYERS)] + \
+               [(n, ctypes.c_void_p) for n in ("dlat", "colmax", "head_part", "log_std_part")] + \
+               [("w_chain_t", ctypes.c_void_p * TAIL_MAX_LAYERS)]
+
+
 MHA_NCOLMAX = 12          # qs_mha_train.colmax rows (QS_MHA_NCOLMAX)
 
 
@@ -237,7 +246,8 @@ EXPORTS = ["qs_abi_version", "qs_last_error", "qs_struct_sizes", "qs_config_defa
            "qs_attn_bwd1_x3", "qs_attn_bwd2_x3", "qs_attn_dw_x3", "qs_attn_dw0_x3", "qs_colmax_reduce", "qs_colstats",
            "qs_linear_tanh_x3", "qs_dw_x3_ld", "qs_linear_rows_x3",
            "qs_tanh_grad_stats", "qs_linear_bias_x3", "qs_slab_sum_stats",
-           "qs_linear_tanh_cat_x3", "qs_mha_encoder_x3", "qs_mha_encoder_train_x3", "qs_mha_bwd_x3", "qs_policy_tail_x3"]
+           "qs_linear_tanh_cat_x3", "qs_mha_encoder_x3", "qs_mha_encoder_train_x3", "qs_mha_bwd_x3", "qs_policy_tail_x3",
+           "qs_policy_tail_train_x3", "qs_policy_tail_bwd_x3"]
 EXPORTS += ["qs_render_config_default", "qs_render_query", "qs_render"]
 EXPORTS += ["qs_shaping_config_default", "qs_shaping_workspace_bytes", "qs_shaping_enable", "qs_shaping_disable",
             "qs_shaping_buffers_get", "qs_shaping_set_training_steps"]
@@ -301,6 +311,8 @@ def lib():
         "qs_mha_encoder_train_x3": ([V, I32, I32, I32, I32, I32, I32, P(QsMhaTower), P(QsMhaTrain), I32, V], I32),
         "qs_mha_bwd_x3": ([I32, I32, P(QsMhaTower), P(QsMhaTrain), I32, V], I32),
         "qs_policy_tail_x3": ([ctypes.c_int64, I32, I32, P(QsTailTower), I32, V], I32),
+        "qs_policy_tail_train_x3": ([ctypes.c_int64, I32, I32, P(QsTailTower), P(QsTailTrain), I32, V], I32),
+        "qs_policy_tail_bwd_x3": ([ctypes.c_int64, I32, I32, P(QsTailTower), P(QsTailTrain), I32, I32, V], I32),
     }
     sig.update({
         "qs_render_config_default": ([P(QsRenderConfig)], I32),

@@ -339,19 +339,27 @@ class SwarmActorCritic(nn.Module):
             actions = torch.tanh(mean + torch.randn_like(mean) * self.log_std.exp())
         return actions, values, squashed_log_prob(mean, self.log_std, actions)
 
-    def evaluate_actions(self, obs, actions, nbr=None, l0=None, ff=None):
+    def evaluate_actions(self, obs, actions, nbr=None, l0=None, ff=None, tail=None):
         """(values, log_prob, entropy=None) -- ActorCriticPolicyCustom.py:538-566.  nbr: (actor, critic) neighbour
         encoder outputs from the fused update (encoder_train.FusedAttentionTrain; for the multi-head attention encoder
         its two towers' tokens, mha_train.FusedMhaTrain), else the torch encoders run;
         l0 / ff: the fused update's self-encoder first layer and feed_forward (FusedAttentionTrain.self_layer0 /
-        .feed_forward), with nbr only."""
+        .feed_forward), with nbr only;
+        tail: tail(lat_actor, lat_critic, actions) -> (values, log_prob) from the encoders' outputs, in place of the
+        cores, decoders, heads and the log-prob below (tail_train.FusedTailTrain.evaluate), with or without nbr."""
         if nbr is None:
+            if tail is not None:
+                values, log_prob = tail(self.actor_encoder(obs), self.critic_encoder(obs), actions)
+                return values, log_prob, None
             mean = self.action_net(self.actor_latent(obs))
             return self.predict_values(obs), squashed_log_prob(mean, self.log_std, actions), None
         if self.cfg.encoder_type == "attention":   # nbr: the two towers' attention tokens (mha_train.FusedMhaTrain)
             enc = lambda e, tok: e(obs, tokens=tok)  # noqa: E731
         else:
             enc = lambda e, out: e(obs, out, l0, ff)  # noqa: E731
+        if tail is not None:
+            values, log_prob = tail(enc(self.actor_encoder, nbr[0]), enc(self.critic_encoder, nbr[1]), actions)
+            return values, log_prob, None
         mean = head_linear(self.action_net, self.actor_decoder(self.actor_core(enc(self.actor_encoder, nbr[0]))))
         values = head_linear(self.value_net, self.critic_decoder(self.critic_core(enc(self.critic_encoder, nbr[1]))))
         return values, squashed_log_prob(mean, self.log_std, actions), None
@@ -573,11 +581,13 @@ class PPOTrainer:
 
     def __init__(self, env, policy: SwarmActorCritic, cfg: PPOConfig = None, device=None, seed=0,
                  gae_fn=None, group=None, fused_rollout=True, rollout_precision="fp32", update_precision="fp32",
-                 mha_update="torch", rollout_tail="torch"):
+                 mha_update="torch", rollout_tail="torch", update_tail="torch"):
         import torch.distributed as dist
 
         if rollout_tail not in ("torch", "x3"):
             raise ValueError("rollout_tail must be 'torch' or 'x3'")
+        if update_tail not in ("torch", "x3"):
+            raise ValueError("update_tail must be 'torch' or 'x3'")
 
         self.env, self.policy, self.cfg = env, policy, cfg or PPOConfig()
         self.device = torch.device(device) if device is not None else next(policy.parameters()).device
@@ -642,6 +652,16 @@ class PPOTrainer:
                 raise NAT.QuadSwarmError("mha_update='x3' needs a HIP device")
             from .mha_train import FusedMhaTrain
             self.fused_mha = FusedMhaTrain(policy)
+        # update_tail "x3": what follows the encoders in the update (cores, decoders, heads, the stored actions' log-prob),
+        # forward and backward, as one autograd node on the tail kernels (tail_train.py) instead of torch autograd; a
+        # chain weight beyond the split-f16 range sends that minibatch's tail back to torch (with a warning)
+        self.update_tail = update_tail
+        self.fused_tail = None
+        if update_tail == "x3":
+            if self.device.type != "cuda":
+                raise NAT.QuadSwarmError("update_tail='x3' needs a HIP device")
+            from .tail_train import FusedTailTrain
+            self.fused_tail = FusedTailTrain(policy)   # ValueError for a policy the kernels do not cover
 
     def reset(self):
         self.last_obs = self.env.reset()
@@ -751,7 +771,8 @@ class PPOTrainer:
                     nbr = fused_mha.tokens(ob)   # None: a weight out of range, this minibatch on torch autograd
                 values, logp, entropy = pol.evaluate_actions(ob, act[idx], nbr=nbr,
                                                              l0=fused.self_layer0 if fused and nbr is not None else None,
-                                                             ff=fused.feed_forward if fused and nbr is not None else None)
+                                                             ff=fused.feed_forward if fused and nbr is not None else None,
+                                                             tail=self.fused_tail)
                 values = values.flatten()
                 adv = adv_all[idx]
                 if c.normalize_advantage and idx.numel() > 1:

@@ -1,14 +1,19 @@
 #!/usr/bin/env python
 """HIP-event times and launch counts of one rollout policy evaluation with the torch tail against the fused tail
 (csrc/qs_policy_tail.h, FusedRolloutPolicy(tail="x3")) on the same inputs in the same process ("the policy
-tail").
+tail"); with --update, of the PPO update's tail (csrc/qs_policy_tail_train.h, PPOTrainer(update_tail="x3")) against torch
+autograd.
 
-    python tools/policy_tail_time.py [--B 32768] [--iters 50] [--rounds 3]
+    python tools/policy_tail_time.py [--B 32768] [--iters 50] [--rounds 3] [--update [--envs 512] [--steps 8]]
 
 Two policies: C3's default (rnn_size 256, identity core, act_dim 4) and sb_train's (rnn_size 128, 6 core layers).  For
 each, mha_time.py's method (per round, alternating windows of `iters` back-to-back calls between two events, after
 warm-up) on the whole evaluation forward(obs) and on the tail alone (tail() on fixed latents and noise), then, in a
-separate pass with the timing done, the device launches of one call of each counted with torch.profiler."""
+separate pass with the timing done, the device launches of one call of each counted with torch.profiler.
+
+--update: the same windows on forward + backward of the tail alone (fixed latents, actions and upstream gradients at
+the PPO scale 1e-3; gradients for both latents and every tail parameter) and on one whole train(max_updates=1)
+minibatch of B rows on a C3 env of --envs x 8 agents and --steps steps, with update_tail "torch" and "x3"."""
 import argparse
 import json
 import os
@@ -38,11 +43,64 @@ def launches(fn):
     return sum(1 for e in prof.events() if e.device_type == DeviceType.CUDA)
 
 
+def measure(fns, a, **info):
+    """Warm-up, then per round one window of every function in turn; launch counts afterwards.  One JSON line."""
+    for _ in range(5):
+        for f in fns.values():
+            f()
+    ms = {k: [] for k in fns}
+    for _ in range(a.rounds):
+        for k, f in fns.items():
+            ms[k].append(window(f, a.iters))
+    n = {k: launches(f) for k, f in fns.items()}
+    best = {k: min(v) for k, v in ms.items()}
+    print(json.dumps(dict(ms=ms, launches=n, **info, **{k[:-3] + "_speedup": best[k[:-3] + "_torch"] / best[k]
+                                                         for k in fns if k.endswith("_x3")})))
+
+
+def update_mode(a):
+    from quadswarm_amd import QuadSwarmConfig
+    from quadswarm_amd.env import QuadSwarmEnv
+    from quadswarm_amd.ppo import PPOConfig, PPOTrainer
+    from quadswarm_amd.tail_train import FusedTailTrain, torch_tail
+
+    cfg = QuadSwarmConfig(num_envs=a.envs, seed=3)
+    env = QuadSwarmEnv(cfg)
+    for name, make in (("c3_default", PolicyConfig.for_env), ("sb_train", PolicyConfig.sb_train)):
+        torch.manual_seed(0)
+        pol = SwarmActorCritic(make(cfg)).cuda()
+        pc, B = pol.cfg, a.B
+        lat = torch.tanh(torch.randn(2, B, 2 * pc.rnn_size, device="cuda")).requires_grad_()
+        act = torch.rand(B, pc.act_dim, device="cuda") * 1.6 - 0.8
+        dv, dl = torch.randn(B, 1, device="cuda") * 1e-3, torch.randn(B, device="cuda") * 1e-3
+        fused = FusedTailTrain(pol)
+        wrt = [lat] + fused.params()
+
+        def fwd_bwd(tail):
+            v, lp = tail(lat[0], lat[1], act)
+            return torch.autograd.grad((v * dv).sum() + (lp * dl).sum(), wrt)
+
+        fns = {"tail_torch": lambda: fwd_bwd(lambda *x: torch_tail(pol, *x)), "tail_x3": lambda: fwd_bwd(fused)}
+        ref = fns["tail_torch"]()
+        diff = max(((x - y).abs().max() / y.abs().max()).item() for x, y in zip(fns["tail_x3"](), ref))
+        for mode in ("torch", "x3"):
+            tr = PPOTrainer(env, pol, PPOConfig(n_steps=a.steps, batch_size=B, n_epochs=1), seed=1, rollout_precision="x3",
+                            update_tail=mode)
+            assert tr.collect_rollouts() and tr.storage.T * tr.storage.I >= B
+            fns["minibatch_" + mode] = lambda tr=tr: tr.train(max_updates=1)
+        measure(fns, a, policy=name, B=B, R=pc.rnn_size, n_layers=len(fused.runner.chains[0]),
+                max_rel_grad_diff_tail_vs_torch_fp32=diff)
+    env.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    for name, default in (("B", 32768), ("iters", 50), ("rounds", 3)):
+    for name, default in (("B", 32768), ("iters", 50), ("rounds", 3), ("envs", 512), ("steps", 8)):
         ap.add_argument("--" + name, type=int, default=default)
+    ap.add_argument("--update", action="store_true")
     a = ap.parse_args()
+    if a.update:
+        return update_mode(a)
     for name, kw in POLICIES.items():
         torch.manual_seed(0)
         pc = PolicyConfig(**kw)
@@ -59,19 +117,8 @@ def main():
             fns["forward_" + mode] = lambda fp=fp: fp(obs)
             fns["tail_" + mode] = lambda fp=fp: fp.tail(lat[0], lat[1], noise)
         diff = max((x - y).abs().max().item() for x, y in zip(fns["tail_x3"](), fns["tail_torch"]()))
-        for _ in range(5):
-            for f in fns.values():
-                f()
-        ms = {k: [] for k in fns}
-        for _ in range(a.rounds):
-            for k, f in fns.items():
-                ms[k].append(window(f, a.iters))
-        n = {k: launches(f) for k, f in fns.items()}
-        best = {k: min(v) for k, v in ms.items()}
-        print(json.dumps(dict(policy=name, B=B, R=R, n_layers=pc.rnn_num_layers if pc.rnn_type == "full" else 0,
-                              ms=ms, launches=n, max_abs_diff_tail_vs_torch_fp32=diff,
-                              tail_speedup=best["tail_torch"] / best["tail_x3"],
-                              forward_speedup=best["forward_torch"] / best["forward_x3"])))
+        measure(fns, a, policy=name, B=B, R=R, n_layers=pc.rnn_num_layers if pc.rnn_type == "full" else 0,
+                max_abs_diff_tail_vs_torch_fp32=diff)
 
 
 if __name__ == "__main__":
