@@ -792,6 +792,48 @@ int qs_policy_tail_train_x3(int64_t B, int32_t R, int32_t n_layers, const qs_tai
 int qs_policy_tail_bwd_x3(int64_t B, int32_t R, int32_t n_layers, const qs_tail_tower* towers, const qs_tail_train* trains,
                           int32_t n_towers, int32_t grid_x, void* stream);
 
+/* Fused no-grad forward of QuadMultiEncoder (swarm_rl/models/quad_multi_model.py:250-353) for the neighbour encoders
+ * that are plain MLPs (csrc/qs_policy_enc.h; new symbols, the ABI version is unchanged): per agent, every layer Linear +
+ * Tanh of width H (128 or 256) on the split-f16 matrix cores,
+ *   self_encoder (2 layers) on obs[:self_dim];
+ *   the neighbour encoder on obs[self_dim : self_dim + K nbr_dim]: QS_ENC_NBR_MLP, neighbor_mlp (3 layers) on the whole
+ *     block; QS_ENC_NBR_MEAN, the mean over k < K of embedding_mlp (2 layers) on neighbour k; QS_ENC_NBR_NONE, none (the
+ *     block is skipped);
+ *   obstacle_encoder (2 layers) on the obst_dim values that follow the neighbour block, when obst_dim > 0;
+ *   out = tanh([self | neighbour | obstacle] W_ff^T + b_ff), [B, 2H]: what qs_policy_tail_x3 reads as x.
+ * One launch, up to QS_ATTN_MAX_TOWERS towers, nothing but obs read and out written.  Every pointer is device memory;
+ * w_*p are packed as for qs_attn_embed_x3 (quadswarm_amd.policy_fused.pack_mfma_weight_x3), layer 0 of a branch with
+ * its input columns zero-padded to the width given below. */
+typedef enum qs_enc_nbr_kind { QS_ENC_NBR_NONE = 0, QS_ENC_NBR_MEAN = 1, QS_ENC_NBR_MLP = 2 } qs_enc_nbr_kind;
+typedef struct qs_enc_tower {
+    const void* w_s1p;     /* packed [H, 32]: self_encoder[0].weight (self_dim columns) | 0 ..                      */
+    const float* b_s1;     /* [H] */
+    const void* w_s2p;     /* packed self_encoder[2].weight */
+    const float* b_s2;
+    const void* w_n1p;     /* MLP: packed [H, 64] neighbor_mlp[0].weight (K nbr_dim columns) | 0 ..; MEAN: packed [H, 16]
+                              embedding_mlp[0].weight (nbr_dim columns) | 0 ..; NONE: not read                       */
+    const float* b_n1;
+    const void* w_n2p;     /* packed second neighbour layer (MLP, MEAN) */
+    const float* b_n2;
+    const void* w_n3p;     /* packed neighbor_mlp[4].weight (MLP) */
+    const float* b_n3;
+    const void* w_o1p;     /* packed [H, 16]: obstacle_encoder[0].weight (obst_dim columns) | 0 .. (obst_dim > 0)    */
+    const float* b_o1;
+    const void* w_o2p;     /* packed obstacle_encoder[2].weight (obst_dim > 0) */
+    const float* b_o2;
+    const void* w_ffp;     /* the packed [H, H] blocks feed_forward[0].weight[zH:(z+1)H, pH:(p+1)H], contiguous in (z, p)
+                              order: z < 2 output halves, p < (number of parts present) in the order self, neighbour,
+                              obstacle                                                                               */
+    const float* b_ff;     /* [2H] */
+    float* out;            /* [B, 2H] out */
+} qs_enc_tower;
+/* obs: [B, obs_stride] rows.  self_dim 1..32; MLP: K nbr_dim 1..64; MEAN: K >= 1, nbr_dim 1..16; NONE: K and nbr_dim
+ * only place the obstacle values; obst_dim 0..16; self_dim + K nbr_dim + obst_dim <= obs_stride; B >= 1.  The caller
+ * guarantees the split-f16 ranges |obs| < 4094 and |w| < 255.9 for every packed weight.  Asynchronous on `stream`. */
+int qs_encoder_mlp_x3(const float* d_obs, int32_t obs_stride, int32_t self_dim, int32_t nbr_kind, int32_t K,
+                      int32_t nbr_dim, int32_t obst_dim, int32_t B, int32_t H, const qs_enc_tower* towers,
+                      int32_t n_towers, void* stream);
+
 /* sb_train's capture-radius curriculum on the device (ABI 11; replaces CurriculumCallback._on_step,
  * swarm_rl/custom_callbacks.py:441-468, which SB3 runs after every VecEnv step).  Flavor A.  The callback's state
  * is a qs_curriculum in DEVICE memory; qs_curriculum_step, enqueued after a qs_step, records the outcome of every

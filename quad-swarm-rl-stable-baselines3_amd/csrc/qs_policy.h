@@ -36,7 +36,8 @@
 //                       the rollout's attn_pool_x3_kernel, the feed_forward linear_tanh_x3_kernel
 //   qs_policy_train.h : the update's attn_pool_train_x3_kernel (the forward with saves), the backward, dW, statistics
 // (qs_policy_mha.h, the multi-head attention encoder of the obstacle policies, builds on qs_policy_x3.h in a translation
-// unit of its own, qs_policy_mha.hip.)
+// unit of its own, qs_policy_mha.hip; so do qs_policy_tail.h, the rollout policy's tail, and qs_policy_enc.h, the
+// rollout encoder of the mlp / mean_embed / no_encoder families.)
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>

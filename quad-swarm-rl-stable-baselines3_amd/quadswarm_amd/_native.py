@@ -195,6 +195,15 @@ class QsTailTrain(ctypes.Structure):
                [("w_chain_t", ctypes.c_void_p * TAIL_MAX_LAYERS)]
 
 
+ENC_NBR = {"none": 0, "mean": 1, "mlp": 2}   # qs_enc_nbr_kind
+
+
+class QsEncTower(ctypes.Structure):
+    """qs_enc_tower (device pointers of one MLP-family QuadMultiEncoder tower, quadswarm.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("w_s1p", "b_s1", "w_s2p", "b_s2", "w_n1p", "b_n1", "w_n2p", "b_n2", "w_n3p",
+                                                "b_n3", "w_o1p", "b_o1", "w_o2p", "b_o2", "w_ffp", "b_ff", "out")]
+
+
 MHA_NCOLMAX = 12          # qs_mha_train.colmax rows (QS_MHA_NCOLMAX)
 
 
@@ -247,7 +256,7 @@ EXPORTS = ["qs_abi_version", "qs_last_error", "qs_struct_sizes", "qs_config_defa
            "qs_linear_tanh_x3", "qs_dw_x3_ld", "qs_linear_rows_x3",
            "qs_tanh_grad_stats", "qs_linear_bias_x3", "qs_slab_sum_stats",
            "qs_linear_tanh_cat_x3", "qs_mha_encoder_x3", "qs_mha_encoder_train_x3", "qs_mha_bwd_x3", "qs_policy_tail_x3",
-           "qs_policy_tail_train_x3", "qs_policy_tail_bwd_x3"]
+           "qs_policy_tail_train_x3", "qs_policy_tail_bwd_x3", "qs_encoder_mlp_x3"]
 EXPORTS += ["qs_render_config_default", "qs_render_query", "qs_render"]
 EXPORTS += ["qs_shaping_config_default", "qs_shaping_workspace_bytes", "qs_shaping_enable", "qs_shaping_disable",
             "qs_shaping_buffers_get", "qs_shaping_set_training_steps"]
@@ -313,6 +322,7 @@ def lib():
         "qs_policy_tail_x3": ([ctypes.c_int64, I32, I32, P(QsTailTower), I32, V], I32),
         "qs_policy_tail_train_x3": ([ctypes.c_int64, I32, I32, P(QsTailTower), P(QsTailTrain), I32, V], I32),
         "qs_policy_tail_bwd_x3": ([ctypes.c_int64, I32, I32, P(QsTailTower), P(QsTailTrain), I32, I32, V], I32),
+        "qs_encoder_mlp_x3": ([V, I32, I32, I32, I32, I32, I32, I32, I32, P(QsEncTower), I32, V], I32),
     }
     sig.update({
         "qs_render_config_default": ([P(QsRenderConfig)], I32),

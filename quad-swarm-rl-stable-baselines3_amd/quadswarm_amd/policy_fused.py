@@ -18,7 +18,12 @@ A policy built with encoder_type "attention" (the obstacle runs' QuadMultiHeadAt
 towers from the observations to the two normalised attention tokens per agent; the self encoder and feed_forward
 stay in torch (the self encoder's second layer on qs_linear_tanh_x3 where it fits).  tests/test_gpu_policy_mha.py.
 
-tail="x3" (either family): everything after the feed_forward -- core, decoder, action_net / value_net, the squashed
+A QuadMultiEncoder whose neighbour encoder is a plain MLP (mean_embed, mlp, or none) is the third family
+(encoder_supports): with precision "x3" one launch of qs_encoder_mlp_x3 (csrc/qs_policy_enc.h) takes both towers from
+the observations to the feed_forward output, so with tail "x3" a rollout step is two launches.
+tests/test_gpu_policy_encoder.py.
+
+tail="x3" (any family): everything after the feed_forward -- core, decoder, action_net / value_net, the squashed
 Gaussian's sampling and log-prob -- is one launch of qs_policy_tail_x3 (csrc/qs_policy_tail.h) for both towers in place
 of the torch row above.  tests/test_gpu_policy_tail.py.
 """
@@ -193,6 +198,102 @@ def supports(policy):
             c.num_use_neighbor_obs <= 64 and c.self_obs_dim + c.neighbor_obs_dim <= 32 and c.nonlinearity == "tanh")
 
 
+ENC_SW, ENC_NBW, ENC_NDW, ENC_OBW = 32, 64, 16, 16   # layer-0 contraction widths of qs_encoder_mlp_x3 (csrc/qs_policy_enc.h)
+
+
+def enc_nbr_kind(cfg):
+    """The neighbour branch qs_encoder_mlp_x3 evaluates for an encoder_type "mlp" policy: "none", "mean", "mlp", or
+    None for a neighbour encoder it does not have (attention)."""
+    if cfg.num_use_neighbor_obs == 0 or cfg.neighbor_encoder_type == "no_encoder":
+        return "none"
+    return {"mean_embed": "mean", "mlp": "mlp"}.get(cfg.neighbor_encoder_type)
+
+
+def encoder_supports(policy):
+    """Can qs_encoder_mlp_x3 (csrc/qs_policy_enc.h) evaluate this policy's encoders, observations to feed_forward
+    output?  QuadMultiEncoder with the mean_embed, mlp or no neighbour encoder; tanh; every branch rnn_size (128 or 256)
+    wide; self <= 32, the mlp block <= 64, one mean_embed neighbour <= 16 and the obstacle values <= 16 columns."""
+    c = policy.cfg
+    kind = enc_nbr_kind(c) if c.encoder_type == "mlp" else None
+    if kind is None or c.nonlinearity != "tanh" or c.rnn_size not in (128, 256):
+        return False
+    if kind != "none" and c.neighbor_hidden_size != c.rnn_size:
+        return False
+    if c.obstacle_obs_dim and c.obst_hidden_size != c.rnn_size:
+        return False
+    if kind == "mlp" and not 1 <= c.neighbor_obs_dim * c.num_use_neighbor_obs <= ENC_NBW:
+        return False
+    if kind == "mean" and not 1 <= c.neighbor_obs_dim <= ENC_NDW:
+        return False
+    return 1 <= c.self_obs_dim <= ENC_SW and 0 <= c.obstacle_obs_dim <= ENC_OBW
+
+
+def enc_tower_mats(enc):
+    """One QuadMultiEncoder tower's matrices as qs_enc_tower takes them, before packing: {name: [N, Kd] fp32}, each
+    branch's layer 0 zero-padded to its contraction width, and "w_ffp" the list of the feed_forward's H x H blocks
+    W[zH:(z+1)H, pH:(p+1)H] in (z, p) order."""
+    c, H = enc.cfg, enc.cfg.rnn_size
+
+    def pad(w, width):
+        out = torch.zeros(H, width, dtype=torch.float32, device=w.device)
+        out[:, :w.shape[1]] = w.detach()
+        return out
+    se = enc.self_encoder
+    m = dict(w_s1p=pad(se[0].weight, ENC_SW), w_s2p=se[2].weight)
+    kind = enc_nbr_kind(c)
+    if kind == "mlp":
+        nm = enc.neighbor_encoder.neighbor_mlp
+        m.update(w_n1p=pad(nm[0].weight, ENC_NBW), w_n2p=nm[2].weight, w_n3p=nm[4].weight)
+    elif kind == "mean":
+        em = enc.neighbor_encoder.embedding_mlp
+        m.update(w_n1p=pad(em[0].weight, ENC_NDW), w_n2p=em[2].weight)
+    if enc.obstacle_encoder is not None:
+        oe = enc.obstacle_encoder
+        m.update(w_o1p=pad(oe[0].weight, ENC_OBW), w_o2p=oe[2].weight)
+    wff = enc.feed_forward[0].weight
+    assert wff.shape[0] == 2 * H and wff.shape[1] % H == 0
+    m["w_ffp"] = [wff[z * H:(z + 1) * H, p * H:(p + 1) * H] for z in range(2) for p in range(wff.shape[1] // H)]
+    return m
+
+
+def enc_tower_biases(enc):
+    c = enc.cfg
+    se = enc.self_encoder
+    b = dict(b_s1=se[0].bias, b_s2=se[2].bias, b_ff=enc.feed_forward[0].bias)
+    kind = enc_nbr_kind(c)
+    if kind == "mlp":
+        nm = enc.neighbor_encoder.neighbor_mlp
+        b.update(b_n1=nm[0].bias, b_n2=nm[2].bias, b_n3=nm[4].bias)
+    elif kind == "mean":
+        em = enc.neighbor_encoder.embedding_mlp
+        b.update(b_n1=em[0].bias, b_n2=em[2].bias)
+    if enc.obstacle_encoder is not None:
+        b.update(b_o1=enc.obstacle_encoder[0].bias, b_o2=enc.obstacle_encoder[2].bias)
+    return {k: v.detach().contiguous() for k, v in b.items()}
+
+
+def pack_enc_towers(encs):
+    """Every tower's qs_enc_tower operands: the matrices of enc_tower_mats packed in one pack_mfma_weights_x3 batch (the
+    feed_forward's blocks stacked, contiguous) plus the bias vectors.  ValueError for a weight out of the f16 range."""
+    mats = [enc_tower_mats(enc) for enc in encs]
+    flat, where = [], []
+    for i, m in enumerate(mats):
+        for name, w in m.items():
+            for w1 in (w if name == "w_ffp" else [w]):
+                flat.append(w1)
+                where.append((i, name))
+    pk = pack_mfma_weights_x3(flat)
+    out = [enc_tower_biases(enc) for enc in encs]
+    for (i, name), t in zip(where, pk):
+        if name == "w_ffp":
+            out[i].setdefault(name, []).append(t)
+        else:
+            out[i][name] = t.contiguous()
+    for w in out:
+        w["w_ffp"] = torch.stack(w["w_ffp"]).contiguous()
+    return out
+
+
 def tail_chain(core, decoder):
     """The Linear layers of a tower's core followed by its decoder's: the chain qs_policy_tail_x3 evaluates."""
     return [m for m in list(core) + list(decoder) if isinstance(m, torch.nn.Linear)]
@@ -279,13 +380,15 @@ class FusedRolloutPolicy:
         self.precision = precision
         self.packed_precision = None   # what refresh() packed: precision, or fp32 when x3 weights are out of range
         self._obs_absmax = None        # running max |obs| the x3 layer 0 has seen since the last check_inputs()
-        if not supports(policy):
+        # the MLP family (QuadMultiEncoder with the mean_embed, mlp or no neighbour encoder, csrc/qs_policy_enc.h): x3 only
+        self.enc = not supports(policy) and encoder_supports(policy)
+        if not supports(policy) and not self.enc:
             raise ValueError("fused rollout forward: needs the tanh attention encoder with hidden size 128 or 256")
         self.policy = policy
         self.cfg = policy.cfg
         # the multi-head attention encoder family (encoder_type "attention", csrc/qs_policy_mha.h): x3 only
         self.mha = self.cfg.encoder_type == "attention"
-        self.H = self.cfg.rnn_size if self.mha else self.cfg.neighbor_hidden_size
+        self.H = self.cfg.rnn_size if self.mha or self.enc else self.cfg.neighbor_hidden_size
         self.K = self.cfg.num_use_neighbor_obs
         self.nd = self.cfg.neighbor_obs_dim
         self.so = self.cfg.self_obs_dim
@@ -293,7 +396,8 @@ class FusedRolloutPolicy:
         self.L = NAT.lib()
         self.B = None
         self.packed = None
-        self.towers = ((NAT.QsMhaTower if self.mha else NAT.QsAttnTower) * NAT.ATTN_MAX_TOWERS)()
+        tower = NAT.QsEncTower if self.enc else NAT.QsMhaTower if self.mha else NAT.QsAttnTower
+        self.towers = (tower * NAT.ATTN_MAX_TOWERS)()
 
     # ---- weights / buffers ----
     def refresh(self):
@@ -303,6 +407,8 @@ class FusedRolloutPolicy:
             self._refresh_tail()
         if self.mha:
             return self._refresh_mha()
+        if self.enc:
+            return self._refresh_enc()
         prec = self.precision
         if prec == "x3":
             lim = F16_MAX / X3_SW
@@ -446,6 +552,58 @@ class FusedRolloutPolicy:
             s = se(obs[:, :self.so])
         return enc.feed_forward(torch.cat((s, tokens), dim=1))
 
+    # ---- the MLP family: mean_embed, mlp and no neighbour encoder ----
+    def _refresh_enc(self):
+        """precision "fp32": the torch modules evaluate this family (it has no fp32-MFMA kernel).  "x3": the kernel,
+        unless a weight is outside the split-f16 range (|w| >= 255.9); then the torch modules, until a later refresh."""
+        self.packed_precision = "torch"
+        self.packed = [{} for _ in self.encs]
+        if self.precision != "x3":
+            return
+        try:
+            packed = pack_enc_towers(self.encs)
+        except ValueError as e:
+            import warnings
+            warnings.warn(f"x3 rollout encoders: {e}; evaluating in torch")
+            return
+        self.packed_precision, self.packed = "x3", packed
+        self._bind_enc()
+
+    def _bind_enc(self):
+        if self.packed_precision != "x3" or self.B is None:
+            return
+        for i, w in enumerate(self.packed):
+            t = self.towers[i]
+            for name, x in w.items():
+                assert x.is_contiguous()
+                setattr(t, name, x.data_ptr())
+            t.out = self.out[i].data_ptr()
+
+    @torch.no_grad()
+    def latents(self, obs):
+        """[T, B, 2 rnn_size]: both towers' encoder outputs (the feed_forward's), the rows tail() reads -- one launch of
+        qs_encoder_mlp_x3 from the raw observations (the tensor is reused by the next call)."""
+        assert self.enc and obs.dim() == 2
+        if self.packed is None:
+            self.refresh()
+        if self.packed_precision != "x3":
+            return torch.stack([enc(obs) for enc in self.encs])
+        assert obs.is_cuda and obs.dtype == torch.float32
+        obs = obs.contiguous()
+        B = obs.shape[0]
+        if self.B != B:
+            self.B = B
+            self.out = torch.empty(len(self.encs), B, 2 * self.H, dtype=torch.float32, device=obs.device)
+            self._bind_enc()
+        m = obs.abs().amax()   # layer 0's range check, on the device (read by check_inputs)
+        self._obs_absmax = m if self._obs_absmax is None else torch.maximum(self._obs_absmax, m)
+        st = ctypes.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        NAT.check(self.L.qs_encoder_mlp_x3(ctypes.c_void_p(obs.data_ptr()), obs.shape[1], self.so,
+                                           NAT.ENC_NBR[enc_nbr_kind(self.cfg)], self.K, self.nd,
+                                           self.cfg.obstacle_obs_dim, B, self.H, self.towers, len(self.encs), st),
+                  "qs_encoder_mlp_x3")
+        return self.out
+
     # ---- the tail: core, decoder, heads, action distribution ----
     def _refresh_tail(self):
         """Pack both towers' chains for qs_policy_tail_x3.  A chain weight outside the split-f16 range (|w| >= 255.9)
@@ -579,6 +737,10 @@ class FusedRolloutPolicy:
         """SwarmActorCritic.forward: (actions, values [B, 1], log_prob [B])."""
         from .ppo import squashed_log_prob
         pol = self.policy
+        if self.enc:   # tail(): one launch, or the torch row (the same draw as randn_like(mean) below)
+            lat = self.latents(obs)
+            noise = None if deterministic else torch.randn((obs.shape[0], self.cfg.act_dim), device=obs.device)
+            return self.tail(lat[0], lat[1], noise, deterministic)
         nbr = self.neighbor_encodings(obs)
         if self.tail_mode == "x3":
             lat = [self._encode(enc, obs, nbr[i], self.packed[i]) for i, enc in enumerate(self.encs)]
@@ -600,6 +762,8 @@ class FusedRolloutPolicy:
     @torch.no_grad()
     def predict_values(self, obs):
         pol = self.policy
+        if self.enc:
+            return self.tail(None, self.latents(obs)[1])[1]
         nbr = self.neighbor_encodings(obs)
         if self.tail_mode == "x3":
             return self.tail(None, self._encode(pol.critic_encoder, obs, nbr[1], self.packed[1]))[1]

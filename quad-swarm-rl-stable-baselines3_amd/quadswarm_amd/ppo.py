@@ -581,9 +581,11 @@ class PPOTrainer:
 
     def __init__(self, env, policy: SwarmActorCritic, cfg: PPOConfig = None, device=None, seed=0,
                  gae_fn=None, group=None, fused_rollout=True, rollout_precision="fp32", update_precision="fp32",
-                 mha_update="torch", rollout_tail="torch", update_tail="torch"):
+                 mha_update="torch", rollout_tail="torch", update_tail="torch", rollout_encoder="torch"):
         import torch.distributed as dist
 
+        if rollout_encoder not in ("torch", "x3"):
+            raise ValueError("rollout_encoder must be 'torch' or 'x3'")
         if rollout_tail not in ("torch", "x3"):
             raise ValueError("rollout_tail must be 'torch' or 'x3'")
         if update_tail not in ("torch", "x3"):
@@ -628,6 +630,15 @@ class PPOTrainer:
             from .policy_fused import FusedRolloutPolicy, supports
             if supports(policy):
                 self.fused = FusedRolloutPolicy(policy, precision=rollout_precision, tail=rollout_tail)
+        # rollout_encoder "x3": a QuadMultiEncoder with the mean_embed, mlp or no neighbour encoder from the observations
+        # to its feed_forward output as one launch of qs_encoder_mlp_x3 per evaluation ("torch": these policies keep
+        # fused None and the module evaluates them)
+        if rollout_encoder == "x3":
+            from .policy_fused import FusedRolloutPolicy, encoder_supports
+            if not (self.device.type == "cuda" and fused_rollout and rollout_precision == "x3" and encoder_supports(policy)):
+                raise ValueError("rollout_encoder='x3' needs a HIP device, fused_rollout=True, rollout_precision='x3' and a "
+                                 "policy policy_fused.encoder_supports accepts")
+            self.fused = FusedRolloutPolicy(policy, precision="x3", tail=rollout_tail)
         if rollout_tail == "x3" and self.fused is None:
             raise ValueError("rollout_tail='x3' needs the fused rollout (fused_rollout=True and a policy it supports)")
         # the update's neighbour encoders: torch autograd ("fp32") or the fused split-f16 kernels ("x3",

@@ -93,12 +93,43 @@ def update_mode(a):
     env.close()
 
 
+# --encoder: the MLP-family policies (csrc/qs_policy_enc.h): sb_train's shape with the mlp neighbour encoder, and the
+# obstacle baseline's (no_encoder over 2 skipped pos_vel neighbours, 9 obstacle values, rnn_size 256)
+ENC_POLICIES = {"sb_train_mlp": dict(self_obs_dim=18, neighbor_obs_dim=6, num_use_neighbor_obs=6, act_dim=4, rnn_size=128,
+                                     neighbor_hidden_size=128, rnn_type="full", rnn_num_layers=6,
+                                     neighbor_encoder_type="mlp"),
+                "obst_no_encoder": dict(self_obs_dim=19, neighbor_obs_dim=6, num_use_neighbor_obs=2, obstacle_obs_dim=9,
+                                        act_dim=4, neighbor_encoder_type="no_encoder")}
+
+
+def encoder_mode(a):
+    """One rollout policy step: the torch module (what the rollout runs with rollout_encoder "torch") against
+    FusedRolloutPolicy(pol, "x3", tail="x3") (qs_encoder_mlp_x3 + qs_policy_tail_x3), and the encoder launch alone."""
+    for name, kw in ENC_POLICIES.items():
+        torch.manual_seed(0)
+        pc = PolicyConfig(**kw)
+        pol = SwarmActorCritic(pc).cuda().eval()
+        obs = torch.randn(a.B, pc.self_obs_dim + pc.neighbor_obs_dim * pc.num_use_neighbor_obs + pc.obstacle_obs_dim,
+                          device="cuda")
+        fp = FusedRolloutPolicy(pol, "x3", tail="x3")
+        fp.refresh()
+        assert fp.packed_precision == "x3" and fp.packed_tail is not None
+        with torch.no_grad():
+            fns = {"step_torch": lambda: pol(obs), "step_x3": lambda: fp(obs), "encoder_x3": lambda: fp.latents(obs),
+                   "encoder_torch": lambda: (pol.actor_encoder(obs), pol.critic_encoder(obs))}
+            diff = max((x - y).abs().max().item() for x, y in zip(fns["encoder_x3"](), fns["encoder_torch"]()))
+            measure(fns, a, policy=name, B=a.B, R=pc.rnn_size, max_abs_diff_latents_vs_torch_fp32=diff)
+
+
 def main():
     ap = argparse.ArgumentParser()
     for name, default in (("B", 32768), ("iters", 50), ("rounds", 3), ("envs", 512), ("steps", 8)):
         ap.add_argument("--" + name, type=int, default=default)
     ap.add_argument("--update", action="store_true")
+    ap.add_argument("--encoder", action="store_true")
     a = ap.parse_args()
+    if a.encoder:
+        return encoder_mode(a)
     if a.update:
         return update_mode(a)
     for name, kw in POLICIES.items():
