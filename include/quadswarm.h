@@ -834,6 +834,50 @@ int qs_encoder_mlp_x3(const float* d_obs, int32_t obs_stride, int32_t self_dim, 
                       int32_t nbr_dim, int32_t obst_dim, int32_t B, int32_t H, const qs_enc_tower* towers,
                       int32_t n_towers, void* stream);
 
+/* The PPO update's MLP-family encoders (csrc/qs_policy_enc_train.h; new symbols, the ABI version is unchanged): what one
+ * tower's forward saves and its backward reads and writes.  Every array is the caller's device memory; a branch the
+ * policy does not have is not read and may be NULL. */
+#define QS_ENC_NCOLMAX 9
+typedef struct qs_enc_train {
+    float* s1;             /* [B, H] each, forward out, backward in: the self encoder's two tanh outputs                 */
+    float* s2;
+    float* n1;             /* MLP: [B, H] neighbor_mlp's three tanh outputs n1, n2, n3; MEAN: [B K, H] embedding_mlp's   */
+    float* n2;             /*   e1 (n1) and e2 (n2), row b K + k = neighbour k of agent b (qs_colstats's layer-0 pairing) */
+    float* n3;
+    float* m;              /* MEAN: [B, H] the mean over k of e2 (fp32, after the 1 / K)                                  */
+    float* o1;             /* [B, H] each: the obstacle encoder's two tanh outputs (obst_dim > 0)                         */
+    float* o2;
+    const float* dout;     /* [B, 2H] backward in: gradient of towers[i].out                                             */
+    float* dpre_ff;        /* [B, 2H] backward out: gradient of the feed_forward's pre-activations                       */
+    float* dpre_s1;        /* backward out, shaped like the save of the same name: gradients of the pre-activations      */
+    float* dpre_s2;
+    float* dpre_n1;
+    float* dpre_n2;
+    float* dpre_n3;
+    float* dpre_o1;
+    float* dpre_o2;
+    float* dm;             /* MEAN: [B, H] backward out: gradient of m (the feed_forward part's dP / K)                   */
+    float* colmax;         /* [QS_ENC_NCOLMAX, grid_x, H] backward out: per-block column maxima of |dpre| (qs_colmax_reduce
+                              -> qs_dw_x3_ld's column scales; +inf: non-finite): ff columns [0, H), ff [H, 2H), s1, s2,
+                              n1, n2, n3, o1, o2 (zeros for a branch that is absent)                                     */
+    const void* w_s2t;     /* packed W^T of self_encoder[2], */
+    const void* w_n2t;     /*   of the second neighbour layer (MLP, MEAN), */
+    const void* w_n3t;     /*   of neighbor_mlp[4] (MLP), */
+    const void* w_o2t;     /*   of obstacle_encoder[2] (obst_dim > 0) */
+    const void* w_fft;     /* per part p present (self, neighbour, obstacle), contiguous: the packed [H, 2H] transpose of
+                              feed_forward[0].weight[:, pH:(p+1)H] */
+} qs_enc_train;
+/* qs_encoder_mlp_x3 with every tanh layer's output saved in trains[i]; towers[i].out is bitwise qs_encoder_mlp_x3's. */
+int qs_encoder_mlp_train_x3(const float* d_obs, int32_t obs_stride, int32_t self_dim, int32_t nbr_kind, int32_t K,
+                            int32_t nbr_dim, int32_t obst_dim, int32_t B, int32_t H, const qs_enc_tower* towers,
+                            const qs_enc_train* trains, int32_t n_towers, void* stream);
+/* From trains[i].dout and the saves: every dpre array, dm and colmax, by grid_x blocks per tower (1 .. ceil(B / 64)) that
+ * each walk the 64-agent tiles grid_x apart.  The weight gradients are dpre^T (previous layer's save) on qs_dw_x3_ld,
+ * layer 0's on qs_attn_dw0_x3 / qs_colstats (quadswarm_amd.enc_mlp_train). */
+int qs_encoder_mlp_bwd_x3(const float* d_obs, int32_t obs_stride, int32_t self_dim, int32_t nbr_kind, int32_t K,
+                          int32_t nbr_dim, int32_t obst_dim, int32_t B, int32_t H, const qs_enc_tower* towers,
+                          const qs_enc_train* trains, int32_t n_towers, int32_t grid_x, void* stream);
+
 /* sb_train's capture-radius curriculum on the device (ABI 11; replaces CurriculumCallback._on_step,
  * swarm_rl/custom_callbacks.py:441-468, which SB3 runs after every VecEnv step).  Flavor A.  The callback's state
  * is a qs_curriculum in DEVICE memory; qs_curriculum_step, enqueued after a qs_step, records the outcome of every

@@ -204,6 +204,16 @@ class QsEncTower(ctypes.Structure):
                                                 "b_n3", "w_o1p", "b_o1", "w_o2p", "b_o2", "w_ffp", "b_ff", "out")]
 
 
+ENC_NCOLMAX = 9           # qs_enc_train.colmax rows (QS_ENC_NCOLMAX)
+
+
+class QsEncTrain(ctypes.Structure):
+    """qs_enc_train (the PPO update's saves and gradients of one MLP-family encoder tower, quadswarm.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("s1", "s2", "n1", "n2", "n3", "m", "o1", "o2", "dout", "dpre_ff", "dpre_s1",
+                                                "dpre_s2", "dpre_n1", "dpre_n2", "dpre_n3", "dpre_o1", "dpre_o2", "dm",
+                                                "colmax", "w_s2t", "w_n2t", "w_n3t", "w_o2t", "w_fft")]
+
+
 MHA_NCOLMAX = 12          # qs_mha_train.colmax rows (QS_MHA_NCOLMAX)
 
 
@@ -256,7 +266,8 @@ EXPORTS = ["qs_abi_version", "qs_last_error", "qs_struct_sizes", "qs_config_defa
            "qs_linear_tanh_x3", "qs_dw_x3_ld", "qs_linear_rows_x3",
            "qs_tanh_grad_stats", "qs_linear_bias_x3", "qs_slab_sum_stats",
            "qs_linear_tanh_cat_x3", "qs_mha_encoder_x3", "qs_mha_encoder_train_x3", "qs_mha_bwd_x3", "qs_policy_tail_x3",
-           "qs_policy_tail_train_x3", "qs_policy_tail_bwd_x3", "qs_encoder_mlp_x3"]
+           "qs_policy_tail_train_x3", "qs_policy_tail_bwd_x3", "qs_encoder_mlp_x3",
+           "qs_encoder_mlp_train_x3", "qs_encoder_mlp_bwd_x3"]
 EXPORTS += ["qs_render_config_default", "qs_render_query", "qs_render"]
 EXPORTS += ["qs_shaping_config_default", "qs_shaping_workspace_bytes", "qs_shaping_enable", "qs_shaping_disable",
             "qs_shaping_buffers_get", "qs_shaping_set_training_steps"]
@@ -323,6 +334,9 @@ def lib():
         "qs_policy_tail_train_x3": ([ctypes.c_int64, I32, I32, P(QsTailTower), P(QsTailTrain), I32, V], I32),
         "qs_policy_tail_bwd_x3": ([ctypes.c_int64, I32, I32, P(QsTailTower), P(QsTailTrain), I32, I32, V], I32),
         "qs_encoder_mlp_x3": ([V, I32, I32, I32, I32, I32, I32, I32, I32, P(QsEncTower), I32, V], I32),
+        "qs_encoder_mlp_train_x3": ([V, I32, I32, I32, I32, I32, I32, I32, I32, P(QsEncTower), P(QsEncTrain), I32, V], I32),
+        "qs_encoder_mlp_bwd_x3": ([V, I32, I32, I32, I32, I32, I32, I32, I32, P(QsEncTower), P(QsEncTrain), I32, I32, V],
+                                  I32),
     }
     sig.update({
         "qs_render_config_default": ([P(QsRenderConfig)], I32),

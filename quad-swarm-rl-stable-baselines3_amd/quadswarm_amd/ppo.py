@@ -339,14 +339,23 @@ class SwarmActorCritic(nn.Module):
             actions = torch.tanh(mean + torch.randn_like(mean) * self.log_std.exp())
         return actions, values, squashed_log_prob(mean, self.log_std, actions)
 
-    def evaluate_actions(self, obs, actions, nbr=None, l0=None, ff=None, tail=None):
+    def evaluate_actions(self, obs, actions, nbr=None, l0=None, ff=None, tail=None, lat=None):
         """(values, log_prob, entropy=None) -- ActorCriticPolicyCustom.py:538-566.  nbr: (actor, critic) neighbour
         encoder outputs from the fused update (encoder_train.FusedAttentionTrain; for the multi-head attention encoder
         its two towers' tokens, mha_train.FusedMhaTrain), else the torch encoders run;
         l0 / ff: the fused update's self-encoder first layer and feed_forward (FusedAttentionTrain.self_layer0 /
         .feed_forward), with nbr only;
         tail: tail(lat_actor, lat_critic, actions) -> (values, log_prob) from the encoders' outputs, in place of the
-        cores, decoders, heads and the log-prob below (tail_train.FusedTailTrain.evaluate), with or without nbr."""
+        cores, decoders, heads and the log-prob below (tail_train.FusedTailTrain.evaluate), with or without nbr;
+        lat: (actor, critic) encoder outputs [B, 2 rnn_size] computed elsewhere (enc_mlp_train.FusedEncoderTrain.latents),
+        in place of both encoders, with or without tail."""
+        if lat is not None:
+            if tail is not None:
+                values, log_prob = tail(lat[0], lat[1], actions)
+                return values, log_prob, None
+            mean = head_linear(self.action_net, self.actor_decoder(self.actor_core(lat[0])))
+            values = head_linear(self.value_net, self.critic_decoder(self.critic_core(lat[1])))
+            return values, squashed_log_prob(mean, self.log_std, actions), None
         if nbr is None:
             if tail is not None:
                 values, log_prob = tail(self.actor_encoder(obs), self.critic_encoder(obs), actions)
@@ -581,7 +590,8 @@ class PPOTrainer:
 
     def __init__(self, env, policy: SwarmActorCritic, cfg: PPOConfig = None, device=None, seed=0,
                  gae_fn=None, group=None, fused_rollout=True, rollout_precision="fp32", update_precision="fp32",
-                 mha_update="torch", rollout_tail="torch", update_tail="torch", rollout_encoder="torch"):
+                 mha_update="torch", rollout_tail="torch", update_tail="torch", rollout_encoder="torch",
+                 update_encoder="torch"):
         import torch.distributed as dist
 
         if rollout_encoder not in ("torch", "x3"):
@@ -590,6 +600,8 @@ class PPOTrainer:
             raise ValueError("rollout_tail must be 'torch' or 'x3'")
         if update_tail not in ("torch", "x3"):
             raise ValueError("update_tail must be 'torch' or 'x3'")
+        if update_encoder not in ("torch", "x3"):
+            raise ValueError("update_encoder must be 'torch' or 'x3'")
 
         self.env, self.policy, self.cfg = env, policy, cfg or PPOConfig()
         self.device = torch.device(device) if device is not None else next(policy.parameters()).device
@@ -673,6 +685,17 @@ class PPOTrainer:
                 raise NAT.QuadSwarmError("update_tail='x3' needs a HIP device")
             from .tail_train import FusedTailTrain
             self.fused_tail = FusedTailTrain(policy)   # ValueError for a policy the kernels do not cover
+        # update_encoder "x3": a QuadMultiEncoder with the mlp, mean_embed or no neighbour encoder in the update, both towers
+        # from the minibatch's observations to the feed_forward outputs, forward and backward, as one autograd node on the
+        # kernels of enc_mlp_train.py instead of torch autograd; a weight beyond the split-f16 range sends that minibatch's
+        # encoders back to torch (with a warning)
+        self.update_encoder = update_encoder
+        self.fused_enc = None
+        if update_encoder == "x3":
+            if self.device.type != "cuda":
+                raise NAT.QuadSwarmError("update_encoder='x3' needs a HIP device")
+            from .enc_mlp_train import FusedEncoderTrain
+            self.fused_enc = FusedEncoderTrain(policy)   # ValueError for a policy encoder_supports refuses
 
     def reset(self):
         self.last_obs = self.env.reset()
@@ -772,6 +795,7 @@ class PPOTrainer:
         # update, whatever the rollout's precision); a weight out of range falls back per minibatch (encodings -> None)
         fused = self.fused_update if self.fused_update is not None and self.fused_update.obs_in_range(obs) else None
         fused_mha = self.fused_mha if self.fused_mha is not None and self.fused_mha.obs_in_range(obs) else None
+        fused_enc = self.fused_enc if self.fused_enc is not None and self.fused_enc.obs_in_range(obs) else None
         for _ in range(c.n_epochs):
             perm = torch.randperm(n, device=self.device, generator=self.gen)
             for s in range(0, n, c.batch_size):
@@ -783,7 +807,8 @@ class PPOTrainer:
                 values, logp, entropy = pol.evaluate_actions(ob, act[idx], nbr=nbr,
                                                              l0=fused.self_layer0 if fused and nbr is not None else None,
                                                              ff=fused.feed_forward if fused and nbr is not None else None,
-                                                             tail=self.fused_tail)
+                                                             tail=self.fused_tail,
+                                                             lat=fused_enc.latents(ob) if fused_enc is not None else None)
                 values = values.flatten()
                 adv = adv_all[idx]
                 if c.normalize_advantage and idx.numel() > 1:

@@ -4,7 +4,7 @@
 tail"); with --update, of the PPO update's tail (csrc/qs_policy_tail_train.h, PPOTrainer(update_tail="x3")) against torch
 autograd.
 
-    python tools/policy_tail_time.py [--B 32768] [--iters 50] [--rounds 3] [--update [--envs 512] [--steps 8]]
+    python tools/policy_tail_time.py [--B 32768] [--iters 50] [--rounds 3] [--update [--envs 512] [--steps 8]] [--encoder]
 
 Two policies: C3's default (rnn_size 256, identity core, act_dim 4) and sb_train's (rnn_size 128, 6 core layers).  For
 each, mha_time.py's method (per round, alternating windows of `iters` back-to-back calls between two events, after
@@ -13,7 +13,12 @@ separate pass with the timing done, the device launches of one call of each coun
 
 --update: the same windows on forward + backward of the tail alone (fixed latents, actions and upstream gradients at
 the PPO scale 1e-3; gradients for both latents and every tail parameter) and on one whole train(max_updates=1)
-minibatch of B rows on a C3 env of --envs x 8 agents and --steps steps, with update_tail "torch" and "x3"."""
+minibatch of B rows on a C3 env of --envs x 8 agents and --steps steps, with update_tail "torch" and "x3".
+
+--update --encoder: the update's MLP-family encoders (csrc/qs_policy_enc_train.h, PPOTrainer(update_encoder="x3")) at B =
+4 096 and 32 768 for three shapes: the saving forward + backward + every parameter gradient of both towers' encoders alone,
+torch autograd against x3, and one whole train(max_updates=1) minibatch on a synthetic rollout with update_tail "x3" and
+update_encoder "torch" / "x3"; plus the backward kernel alone and the repacking alone (where the x3 time goes)."""
 import argparse
 import json
 import os
@@ -121,6 +126,65 @@ def encoder_mode(a):
             measure(fns, a, policy=name, B=a.B, R=pc.rnn_size, max_abs_diff_latents_vs_torch_fp32=diff)
 
 
+ENC_POLICIES_UPDATE = dict(ENC_POLICIES, c3_mean_embed=dict(self_obs_dim=18, neighbor_obs_dim=6, num_use_neighbor_obs=6,
+                                                            act_dim=4, neighbor_encoder_type="mean_embed"))
+
+
+def update_encoder_mode(a):
+    from types import SimpleNamespace
+
+    from quadswarm_amd import _native as NAT
+    from quadswarm_amd.enc_mlp_train import FusedEncoderTrain
+    from quadswarm_amd.ppo import PPOConfig, PPOTrainer
+
+    for name, kw in ENC_POLICIES_UPDATE.items():
+        for B in (4096, 32768):
+            torch.manual_seed(0)
+            pc = PolicyConfig(**kw)
+            pol = SwarmActorCritic(pc).cuda()
+            od = pc.self_obs_dim + pc.neighbor_obs_dim * pc.num_use_neighbor_obs + pc.obstacle_obs_dim
+            obs = torch.randn(B, od, device="cuda")
+            dout = torch.randn(2, B, 2 * pc.rnn_size, device="cuda") * 1e-3
+            fused = FusedEncoderTrain(pol)
+            wrt = fused.params()
+
+            def fwd_bwd(lat):
+                la, lc = lat(obs)
+                return torch.autograd.grad((la * dout[0]).sum() + (lc * dout[1]).sum(), wrt)
+
+            fns = {"encoders_torch": lambda: fwd_bwd(lambda o: (pol.actor_encoder(o), pol.critic_encoder(o))),
+                   "encoders_x3": lambda: fwd_bwd(fused.latents)}
+            ref = fns["encoders_torch"]()
+            diff = max(((x - y).abs().max() / y.abs().max()).item() for x, y in zip(fns["encoders_x3"](), ref))
+            # a synthetic rollout of one minibatch: the trainer reads nothing of the env but its sizes
+            env = SimpleNamespace(I=B, obs_dim=od, act_dim=pc.act_dim)
+            for mode in ("torch", "x3"):
+                tr = PPOTrainer(env, pol, PPOConfig(n_steps=1, batch_size=B, n_epochs=1, learning_rate=0.0), seed=1,
+                                fused_rollout=False, update_tail="x3", update_encoder=mode)
+                st = tr.storage
+                with torch.no_grad():
+                    st.obs[0].copy_(obs)
+                    act, val, lp = pol(obs)
+                    st.actions[0].copy_(act)
+                    st.values[0].copy_(val.view(-1))
+                    st.log_probs[0].copy_(lp)
+                    st.advantages[0].normal_()
+                    st.returns[0].normal_()
+                fns["minibatch_" + mode] = lambda tr=tr: tr.train(max_updates=1)
+            # where the x3 time goes: the backward kernel alone (on the buffers the last backward left) and the repacking
+            r = fused.runner
+            kept = fused.latents(obs)   # (held: the kernel reads the forward's outputs)
+
+            def bwd_only():
+                for i in range(2):
+                    r.towers[i].out, r.trains[i].dout = kept[i].data_ptr(), dout[i].data_ptr()
+                NAT.check(r.L.qs_encoder_mlp_bwd_x3(*r._args(obs), r.grid_x, r._stream(obs.device)), "qs_encoder_mlp_bwd_x3")
+
+            fns["bwd_kernel_only"] = bwd_only
+            fns["pack_only"] = r._pack
+            measure(fns, a, policy=name, B=B, H=pc.rnn_size, grid_x=r.grid_x, max_rel_grad_diff_x3_vs_torch_fp32=diff)
+
+
 def main():
     ap = argparse.ArgumentParser()
     for name, default in (("B", 32768), ("iters", 50), ("rounds", 3), ("envs", 512), ("steps", 8)):
@@ -128,6 +192,8 @@ def main():
     ap.add_argument("--update", action="store_true")
     ap.add_argument("--encoder", action="store_true")
     a = ap.parse_args()
+    if a.encoder and a.update:
+        return update_encoder_mode(a)
     if a.encoder:
         return encoder_mode(a)
     if a.update:
