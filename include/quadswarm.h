@@ -878,6 +878,45 @@ int qs_encoder_mlp_bwd_x3(const float* d_obs, int32_t obs_stride, int32_t self_d
                           int32_t nbr_dim, int32_t obst_dim, int32_t B, int32_t H, const qs_enc_tower* towers,
                           const qs_enc_train* trains, int32_t n_towers, int32_t grid_x, void* stream);
 
+/* The x3 update's weight gradients as one grouped launch per autograd node (csrc/qs_dw_group.h; new symbols, the ABI
+ * version is unchanged).  A job is one dW = G^T A over R rows, optionally with db = sum_r G[r, :]; a group is up to
+ * QS_DW_GROUP_MAX_JOBS jobs that share H.  Every pointer is device memory. */
+#define QS_DW_GROUP_MAX_JOBS 40
+typedef enum qs_dw_a_kind {
+    QS_DW_A_TANH = 0,      /* wide: A [R, H] tanh outputs, |a| <= 1 (a_cols == H)                                      */
+    QS_DW_A_OBS = 1        /* narrow: 1 .. 64 raw observation columns, |a| < 4094 (the layer-0 split-f16 range)         */
+} qs_dw_a_kind;
+typedef struct qs_dw_job {
+    const float* G;        /* [R, H] gradient rows, ldg floats apart (H .. 4096): may be a column slice of wider rows     */
+    const float* A;        /* row r at A + (r / a_rows_per) lda + (r % a_rows_per) a_inner, a_cols floats                */
+    const float* colmax;   /* [colmax_n, H] column maxima of |G| over row ranges that together cover the R rows (the
+                              backward kernels' per-block maxima; +inf: non-finite).  The kernel takes the maximum over
+                              the rows and derives the power-of-two column scales; colmax_n = 1 for a caller with the
+                              maxima themselves                                                                          */
+    float* dW;             /* [H, a_cols] out, rows ldw floats apart: a block inside a larger matrix is written in place,
+                              the rest of that matrix is not touched                                                     */
+    float* db;             /* [H] out, or NULL                                                                           */
+    int64_t R;
+    int32_t ldg;
+    int32_t lda;           /* wide: H .. 4096; narrow: 1 .. 4096 with (a_rows_per - 1) a_inner + a_cols <= lda           */
+    int32_t a_cols;        /* wide: H; narrow: 1 .. 64                                                                   */
+    int32_t a_kind;        /* qs_dw_a_kind                                                                               */
+    int32_t a_rows_per;    /* narrow: G rows per A row (mean_embed's K neighbours of an agent: K, a_inner = nbr_dim);
+                              else 1                                                                                    */
+    int32_t a_inner;
+    int32_t colmax_n;      /* >= 1 */
+    int32_t ldw;           /* a_cols .. 4096 */
+} qs_dw_job;
+/* bytes of the workspace a group of n_jobs jobs split over `parts` row ranges needs (n_jobs parts (H H + H) floats). */
+int qs_dw_group_workspace(int32_t n_jobs, int32_t H, int32_t parts, size_t* bytes);
+/* Two launches on `stream`: grid (parts, n_jobs) forms every job's per-part products and column sums in the workspace,
+ * then a reduction sums the parts in part order (deterministic) into dW / db.  `jobs` is host memory, copied into the
+ * kernel arguments: a caller keeps the table and rewrites the pointers that change between calls (no device copy, no
+ * synchronisation).  H 128 or 256; 1 <= parts <= 65535; a part's rows (ceil(ceil(R / 16) / parts) 16) times the row stride
+ * must stay below 2^29 floats (32-bit byte offsets: refused, not wrapped); narrow jobs R < 2^31; workspace 16-byte aligned. */
+int qs_dw_group_x3(const qs_dw_job* jobs, int32_t n_jobs, int32_t H, int32_t parts, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
 /* sb_train's capture-radius curriculum on the device (ABI 11; replaces CurriculumCallback._on_step,
  * swarm_rl/custom_callbacks.py:441-468, which SB3 runs after every VecEnv step).  Flavor A.  The callback's state
  * is a qs_curriculum in DEVICE memory; qs_curriculum_step, enqueued after a qs_step, records the outcome of every

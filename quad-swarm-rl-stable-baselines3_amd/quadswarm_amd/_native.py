@@ -214,6 +214,16 @@ class QsEncTrain(ctypes.Structure):
                                                 "colmax", "w_s2t", "w_n2t", "w_n3t", "w_o2t", "w_fft")]
 
 
+DW_GROUP_MAX_JOBS = 40    # QS_DW_GROUP_MAX_JOBS
+DW_A_TANH, DW_A_OBS = 0, 1   # qs_dw_a_kind
+
+
+class QsDwJob(ctypes.Structure):
+    """qs_dw_job (one dW = G^T A of a grouped weight-gradient launch, quadswarm.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("G", "A", "colmax", "dW", "db")] + [("R", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("ldg", "lda", "a_cols", "a_kind", "a_rows_per", "a_inner", "colmax_n", "ldw")]
+
+
 MHA_NCOLMAX = 12          # qs_mha_train.colmax rows (QS_MHA_NCOLMAX)
 
 
@@ -267,7 +277,7 @@ EXPORTS = ["qs_abi_version", "qs_last_error", "qs_struct_sizes", "qs_config_defa
            "qs_tanh_grad_stats", "qs_linear_bias_x3", "qs_slab_sum_stats",
            "qs_linear_tanh_cat_x3", "qs_mha_encoder_x3", "qs_mha_encoder_train_x3", "qs_mha_bwd_x3", "qs_policy_tail_x3",
            "qs_policy_tail_train_x3", "qs_policy_tail_bwd_x3", "qs_encoder_mlp_x3",
-           "qs_encoder_mlp_train_x3", "qs_encoder_mlp_bwd_x3"]
+           "qs_encoder_mlp_train_x3", "qs_encoder_mlp_bwd_x3", "qs_dw_group_workspace", "qs_dw_group_x3"]
 EXPORTS += ["qs_render_config_default", "qs_render_query", "qs_render"]
 EXPORTS += ["qs_shaping_config_default", "qs_shaping_workspace_bytes", "qs_shaping_enable", "qs_shaping_disable",
             "qs_shaping_buffers_get", "qs_shaping_set_training_steps"]
@@ -337,6 +347,8 @@ def lib():
         "qs_encoder_mlp_train_x3": ([V, I32, I32, I32, I32, I32, I32, I32, I32, P(QsEncTower), P(QsEncTrain), I32, V], I32),
         "qs_encoder_mlp_bwd_x3": ([V, I32, I32, I32, I32, I32, I32, I32, I32, P(QsEncTower), P(QsEncTrain), I32, I32, V],
                                   I32),
+        "qs_dw_group_workspace": ([I32, I32, I32, P(SZ)], I32),
+        "qs_dw_group_x3": ([P(QsDwJob), I32, I32, I32, V, SZ, V], I32),
     }
     sig.update({
         "qs_render_config_default": ([P(QsRenderConfig)], I32),

@@ -11,7 +11,9 @@ feed_forward, and their autograd.  Here both towers go from the minibatch's raw 
             pre-activation gradients and per-block column maxima
   weights   dW = dpre^T (the previous layer's save) on qs_dw_x3_ld -- the [2H, NP H] feed_forward weight as its 2 NP blocks
             from column slices of dpre_ff; the self encoder's layer 0 on qs_attn_dw0_x3; the neighbour and obstacle layer 0
-            from qs_colstats's part_x (at most 32 columns a call: the mlp block of up to 64 takes two)
+            from qs_colstats's part_x (at most 32 columns a call: the mlp block of up to 64 takes two); with dw="grouped"
+            every product of the node as one qs_dw_group_x3 call instead (dw_group.py: the column scales, the sums over
+            row parts and the block placement inside the kernels)
 PPOTrainer(update_encoder="x3"); tests/test_gpu_enc_mlp_train.py.
 """
 import ctypes
@@ -60,7 +62,7 @@ def pack_ff_transposes(enc):
 class _Runner:
     """Buffers and launches for one policy's two towers (reused across minibatches of the same size)."""
 
-    def __init__(self, policy, grid_x=None):
+    def __init__(self, policy, grid_x=None, dw="calls"):
         c = policy.cfg
         self.H, self.K, self.nd, self.so, self.od = (c.rnn_size, c.num_use_neighbor_obs, c.neighbor_obs_dim, c.self_obs_dim,
                                                      c.obstacle_obs_dim)
@@ -72,6 +74,10 @@ class _Runner:
         self.trains = (NAT.QsEncTrain * NAT.ATTN_MAX_TOWERS)()
         self.B = None
         self.pending = False
+        self.group = None
+        if dw == "grouped":
+            from .dw_group import Group, plan_encoder
+            self.group = Group(plan_encoder(policy), [p for enc in self.encs for p in tower_params(enc)], self.H)
 
     def _alloc(self, B, dev):
         H, K = self.H, self.K
@@ -98,6 +104,8 @@ class _Runner:
             for n, t in b.items():
                 setattr(self.trains[i], n, t.data_ptr())
             self.buf.append(b)
+        if self.group is not None:
+            self.group.bind(self.buf, [b["colmax"] for b in self.buf], B, K, dev)
 
     def _pack(self):
         """x3-pack both towers with this minibatch's values (the optimiser changed them): the forward's operands
@@ -156,7 +164,10 @@ class _Runner:
         for i in range(2):
             self.trains[i].dout = d[i].data_ptr()
         NAT.check(self.L.qs_encoder_mlp_bwd_x3(*self._args(obs), self.grid_x, self._stream(dev)), "qs_encoder_mlp_bwd_x3")
-        grads = [g for i in range(2) for g in self.weight_grads(self.buf[i], obs)]
+        if self.group is not None:
+            grads = self.group.run([{"obs": obs}] * 2, dev)
+        else:
+            grads = [g for i in range(2) for g in self.weight_grads(self.buf[i], obs)]
         self.pending = False
         self.obs = self.out = None
         return grads
@@ -216,14 +227,17 @@ class _EncTrainFn(torch.autograd.Function):
 class FusedEncoderTrain:
     """Both towers' encoders for the PPO update as one autograd node on the HIP kernels: latents(obs) -> (actor [B, 2H],
     critic [B, 2H]), the `lat` of SwarmActorCritic.evaluate_actions.  One backward per forward (the activations live in
-    reused buffers).  grid_x: a cap on the backward's blocks per tower (default: from the CU count)."""
+    reused buffers).  grid_x: a cap on the backward's blocks per tower (default: from the CU count).  dw: the weight
+    gradients by one launch and torch sum per product ("calls") or as one grouped launch per node ("grouped")."""
 
-    def __init__(self, policy, grid_x=None):
+    def __init__(self, policy, grid_x=None, dw="calls"):
+        if dw not in ("calls", "grouped"):
+            raise ValueError("dw must be 'calls' or 'grouped'")
         if not encoder_supports(policy):
             raise ValueError("fused update encoder: needs a tanh QuadMultiEncoder with the mlp, mean_embed or no neighbour "
                              "encoder, every branch rnn_size (128 or 256) wide (policy_fused.encoder_supports)")
         self.policy = policy
-        self.runner = _Runner(policy, grid_x)
+        self.runner = _Runner(policy, grid_x, dw)
 
     def params(self):
         return [p for enc in self.runner.encs for p in tower_params(enc)]

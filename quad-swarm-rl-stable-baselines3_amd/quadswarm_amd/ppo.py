@@ -591,7 +591,7 @@ class PPOTrainer:
     def __init__(self, env, policy: SwarmActorCritic, cfg: PPOConfig = None, device=None, seed=0,
                  gae_fn=None, group=None, fused_rollout=True, rollout_precision="fp32", update_precision="fp32",
                  mha_update="torch", rollout_tail="torch", update_tail="torch", rollout_encoder="torch",
-                 update_encoder="torch"):
+                 update_encoder="torch", update_dw="calls"):
         import torch.distributed as dist
 
         if rollout_encoder not in ("torch", "x3"):
@@ -602,6 +602,10 @@ class PPOTrainer:
             raise ValueError("update_tail must be 'torch' or 'x3'")
         if update_encoder not in ("torch", "x3"):
             raise ValueError("update_encoder must be 'torch' or 'x3'")
+        if update_dw not in ("calls", "grouped"):
+            raise ValueError("update_dw must be 'calls' or 'grouped'")
+        if update_dw == "grouped" and update_encoder != "x3" and update_tail != "x3":
+            raise ValueError("update_dw='grouped' needs update_encoder='x3' or update_tail='x3'")
 
         self.env, self.policy, self.cfg = env, policy, cfg or PPOConfig()
         self.device = torch.device(device) if device is not None else next(policy.parameters()).device
@@ -678,13 +682,16 @@ class PPOTrainer:
         # update_tail "x3": what follows the encoders in the update (cores, decoders, heads, the stored actions' log-prob),
         # forward and backward, as one autograd node on the tail kernels (tail_train.py) instead of torch autograd; a
         # chain weight beyond the split-f16 range sends that minibatch's tail back to torch (with a warning)
+        # update_dw "grouped": the weight gradients of each x3 update node as one grouped launch (dw_group.py) instead of
+        # one launch and torch sum per product ("calls")
+        self.update_dw = update_dw
         self.update_tail = update_tail
         self.fused_tail = None
         if update_tail == "x3":
             if self.device.type != "cuda":
                 raise NAT.QuadSwarmError("update_tail='x3' needs a HIP device")
             from .tail_train import FusedTailTrain
-            self.fused_tail = FusedTailTrain(policy)   # ValueError for a policy the kernels do not cover
+            self.fused_tail = FusedTailTrain(policy, dw=update_dw)   # ValueError for a policy the kernels do not cover
         # update_encoder "x3": a QuadMultiEncoder with the mlp, mean_embed or no neighbour encoder in the update, both towers
         # from the minibatch's observations to the feed_forward outputs, forward and backward, as one autograd node on the
         # kernels of enc_mlp_train.py instead of torch autograd; a weight beyond the split-f16 range sends that minibatch's
@@ -695,7 +702,7 @@ class PPOTrainer:
             if self.device.type != "cuda":
                 raise NAT.QuadSwarmError("update_encoder='x3' needs a HIP device")
             from .enc_mlp_train import FusedEncoderTrain
-            self.fused_enc = FusedEncoderTrain(policy)   # ValueError for a policy encoder_supports refuses
+            self.fused_enc = FusedEncoderTrain(policy, dw=update_dw)   # ValueError for a policy encoder_supports refuses
 
     def reset(self):
         self.last_obs = self.env.reset()

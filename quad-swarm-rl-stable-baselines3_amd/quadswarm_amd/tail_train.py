@@ -9,7 +9,8 @@ towers go from the feed_forward outputs and the stored actions to (values, log_p
   backward  qs_policy_tail_bwd_x3: per 64-row tile the head's backward and the chain's, writing dpre_l, the latents'
             gradients, per-block column maxima and per-block parts of the head's and log_std's gradients
   weights   dW_l, db_l = dpre_l^T y_{l-1} on qs_dw_x3_ld (layer 0: two column blocks against the two R-wide slices of
-            the latents, row slices of stride 2R); the head's and log_std's gradients are the sums of the block parts
+            the latents, row slices of stride 2R); the head's and log_std's gradients are the sums of the block parts;
+            with dw="grouped" the chain's products as one qs_dw_group_x3 call instead (dw_group.py)
 PPOTrainer(update_tail="x3"); tests/test_gpu_tail_train.py.
 """
 import ctypes
@@ -35,7 +36,7 @@ def torch_tail(policy, lat_actor, lat_critic, actions):
 class _Runner:
     """Buffers and launches for one policy's two towers (reused across minibatches of the same size)."""
 
-    def __init__(self, policy):
+    def __init__(self, policy, dw="calls"):
         c = policy.cfg
         self.R = c.rnn_size
         self.chains = (tail_chain(policy.actor_core, policy.actor_decoder),
@@ -49,6 +50,19 @@ class _Runner:
         self.trains = (NAT.QsTailTrain * NAT.ATTN_MAX_TOWERS)()
         self.B = None
         self.pending = False
+        self.group = None
+        if dw == "grouped" and self.n:   # (no chain: nothing but the heads' part sums)
+            from .dw_group import Group, plan_tail
+            self.group = Group(plan_tail(policy), self.params(), self.R)
+
+    def params(self):
+        """FusedTailTrain.params()."""
+        ps = []
+        for ch, head in zip(self.chains, self.heads):
+            for m in ch:
+                ps += [m.weight, m.bias]
+            ps += [head.weight, head.bias]
+        return ps + [self.log_std]
 
     def _alloc(self, B, dev):
         R, n, Win = self.R, self.n, self.Win
@@ -67,6 +81,9 @@ class _Runner:
                 tr.y[l], tr.dpre[l] = b["y"][l].data_ptr(), b["dpre"][l].data_ptr()
             tr.colmax = b["colmax"].data_ptr() if n else None
             tr.head_part, tr.mean, tr.log_std_part = b["head_part"].data_ptr(), b["mean"].data_ptr(), b["log_std_part"].data_ptr()
+        if self.group is not None:
+            named = [{f"{k}{l}": b[k][l] for k in ("y", "dpre") for l in range(n)} for b in self.buf]
+            self.group.bind(named, [b["colmax"] for b in self.buf], B, 1, dev)
 
     def chain_weights(self):
         return [m.weight for ch in self.chains for m in ch]
@@ -142,6 +159,13 @@ class _Runner:
 
     def weight_grads(self):
         R, n, Win = self.R, self.n, self.Win
+        if self.group is not None:   # the chain's gradients from the group, the heads' and log_std's as below
+            grads = self.group.run([{"lat": lat} for lat in self.lat], self.lat[0].device)
+            for i in range(2):
+                hp = self.buf[i]["head_part"].sum(0)
+                grads[i * (2 * n + 2) + 2 * n:(i + 1) * (2 * n + 2)] = [hp[:, :Win], hp[:, Win]]
+            grads[-1] = self.buf[0]["log_std_part"].sum(0)
+            return grads
         grads = []
         for i in range(2):
             b, lat = self.buf[i], self.lat[i]
@@ -175,25 +199,22 @@ class _TailTrainFn(torch.autograd.Function):
 class FusedTailTrain:
     """Both towers' core, decoder, head and the log-prob of the stored actions for the PPO update as one autograd node on
     the HIP kernels: evaluate(lat_actor, lat_critic, actions) -> (values [B, 1], log_prob [B]), the `tail` hook of
-    SwarmActorCritic.evaluate_actions.  One backward per forward (the activations live in reused buffers)."""
+    SwarmActorCritic.evaluate_actions.  One backward per forward (the activations live in reused buffers).  dw: the chain's
+    weight gradients by one launch and torch sum per product ("calls") or as one grouped launch per node ("grouped")."""
 
-    def __init__(self, policy):
+    def __init__(self, policy, dw="calls"):
+        if dw not in ("calls", "grouped"):
+            raise ValueError("dw must be 'calls' or 'grouped'")
         if not tail_supports(policy):
             raise ValueError("fused update tail: needs tanh core / decoder layers of width rnn_size (128 or 256), at most "
                              f"{NAT.TAIL_MAX_LAYERS} of them, and act_dim <= {NAT.TAIL_MAX_OUT}")
         self.policy = policy
-        self.runner = _Runner(policy)
+        self.runner = _Runner(policy, dw)
 
     def params(self):
         """The parameters evaluate() returns gradients for: per tower (actor, critic) every chain layer's weight and bias,
         then the head's; then log_std."""
-        r = self.runner
-        ps = []
-        for ch, head in zip(r.chains, r.heads):
-            for m in ch:
-                ps += [m.weight, m.bias]
-            ps += [head.weight, head.bias]
-        return ps + [r.log_std]
+        return self.runner.params()
 
     def weights_in_range(self):
         """Every chain weight inside the split-f16 range (|w| < 65504 / 256)?  One host read."""

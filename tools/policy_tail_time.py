@@ -18,7 +18,11 @@ minibatch of B rows on a C3 env of --envs x 8 agents and --steps steps, with upd
 --update --encoder: the update's MLP-family encoders (csrc/qs_policy_enc_train.h, PPOTrainer(update_encoder="x3")) at B =
 4 096 and 32 768 for three shapes: the saving forward + backward + every parameter gradient of both towers' encoders alone,
 torch autograd against x3, and one whole train(max_updates=1) minibatch on a synthetic rollout with update_tail "x3" and
-update_encoder "torch" / "x3"; plus the backward kernel alone and the repacking alone (where the x3 time goes)."""
+update_encoder "torch" / "x3"; plus the backward kernel alone and the repacking alone (where the x3 time goes).
+
+--update [--encoder] --dw grouped: the same windows also with the node's weight gradients as one grouped launch
+(csrc/qs_dw_group.h, PPOTrainer(update_dw="grouped")): "*_grouped" beside "*_x3", which stays the per-product path
+("calls"), launches and ms for both from the same process and rounds."""
 import argparse
 import json
 import os
@@ -86,6 +90,9 @@ def update_mode(a):
             return torch.autograd.grad((v * dv).sum() + (lp * dl).sum(), wrt)
 
         fns = {"tail_torch": lambda: fwd_bwd(lambda *x: torch_tail(pol, *x)), "tail_x3": lambda: fwd_bwd(fused)}
+        if a.dw == "grouped":
+            grouped = FusedTailTrain(pol, dw="grouped")
+            fns["tail_grouped"] = lambda: fwd_bwd(grouped)
         ref = fns["tail_torch"]()
         diff = max(((x - y).abs().max() / y.abs().max()).item() for x, y in zip(fns["tail_x3"](), ref))
         for mode in ("torch", "x3"):
@@ -93,6 +100,11 @@ def update_mode(a):
                             update_tail=mode)
             assert tr.collect_rollouts() and tr.storage.T * tr.storage.I >= B
             fns["minibatch_" + mode] = lambda tr=tr: tr.train(max_updates=1)
+        if a.dw == "grouped":
+            tr = PPOTrainer(env, pol, PPOConfig(n_steps=a.steps, batch_size=B, n_epochs=1), seed=1, rollout_precision="x3",
+                            update_tail="x3", update_dw="grouped")
+            assert tr.collect_rollouts()
+            fns["minibatch_grouped"] = lambda tr=tr: tr.train(max_updates=1)
         measure(fns, a, policy=name, B=B, R=pc.rnn_size, n_layers=len(fused.runner.chains[0]),
                 max_rel_grad_diff_tail_vs_torch_fp32=diff)
     env.close()
@@ -154,13 +166,17 @@ def update_encoder_mode(a):
 
             fns = {"encoders_torch": lambda: fwd_bwd(lambda o: (pol.actor_encoder(o), pol.critic_encoder(o))),
                    "encoders_x3": lambda: fwd_bwd(fused.latents)}
+            if a.dw == "grouped":
+                grouped = FusedEncoderTrain(pol, dw="grouped")
+                fns["encoders_grouped"] = lambda: fwd_bwd(grouped.latents)
             ref = fns["encoders_torch"]()
             diff = max(((x - y).abs().max() / y.abs().max()).item() for x, y in zip(fns["encoders_x3"](), ref))
             # a synthetic rollout of one minibatch: the trainer reads nothing of the env but its sizes
             env = SimpleNamespace(I=B, obs_dim=od, act_dim=pc.act_dim)
-            for mode in ("torch", "x3"):
+            for mode in ("torch", "x3") + (("grouped",) if a.dw == "grouped" else ()):
                 tr = PPOTrainer(env, pol, PPOConfig(n_steps=1, batch_size=B, n_epochs=1, learning_rate=0.0), seed=1,
-                                fused_rollout=False, update_tail="x3", update_encoder=mode)
+                                fused_rollout=False, update_tail="x3", update_encoder="torch" if mode == "torch" else "x3",
+                                update_dw="grouped" if mode == "grouped" else "calls")
                 st = tr.storage
                 with torch.no_grad():
                     st.obs[0].copy_(obs)
@@ -191,6 +207,7 @@ def main():
         ap.add_argument("--" + name, type=int, default=default)
     ap.add_argument("--update", action="store_true")
     ap.add_argument("--encoder", action="store_true")
+    ap.add_argument("--dw", choices=("calls", "grouped"), default="calls")
     a = ap.parse_args()
     if a.encoder and a.update:
         return update_encoder_mode(a)
