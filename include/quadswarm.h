@@ -834,6 +834,40 @@ int qs_encoder_mlp_x3(const float* d_obs, int32_t obs_stride, int32_t self_dim, 
                       int32_t nbr_dim, int32_t obst_dim, int32_t B, int32_t H, const qs_enc_tower* towers,
                       int32_t n_towers, void* stream);
 
+/* The attention families' join (csrc/qs_policy_enc.h enc_join_x3_kernel; new symbols, the ABI version is unchanged): the
+ * no-grad forward of everything between their neighbour kernels and qs_policy_tail_x3, one launch for up to
+ * QS_ATTN_MAX_TOWERS towers.  Per agent, Linear + Tanh layers of width H (128 or 256) on the split-f16 matrix cores:
+ *   s = self_encoder (2 layers) on obs[:self_dim];
+ *   nbr_parts = 1: n = the agent's row of nbr [B, H], QuadNeighborhoodEncoderAttention's pooled output (qs_attn_pool_x3's
+ *     out), |n| <= 1; o = obstacle_encoder (2 layers) on obs[obst_off : obst_off + obst_dim] when obst_dim > 0;
+ *     out = tanh([s | n | o] W_ff^T + b_ff);
+ *   nbr_parts = 2: the agent's row of nbr [B, 2H], QuadMultiHeadAttentionEncoder's two LayerNorm tokens (qs_mha_encoder_x3's
+ *     out); obst_dim = 0 (the obstacle values are inside the tokens); out = tanh([s | token 0 | token 1] W_ff^T + b_ff).
+ * out is [B, 2H]: what qs_policy_tail_x3 reads as x.  nbr is read in place.  Every pointer is device memory; w_*p are
+ * packed as for qs_encoder_mlp_x3. */
+typedef struct qs_join_tower {
+    const void* w_s1p;     /* packed [H, 32]: the self encoder's first weight (self_dim columns) | 0 ..                   */
+    const float* b_s1;     /* [H] */
+    const void* w_s2p;     /* packed second self layer */
+    const float* b_s2;
+    const void* w_o1p;     /* packed [H, 16]: obstacle_encoder[0].weight (obst_dim columns) | 0 .. (obst_dim > 0)         */
+    const float* b_o1;
+    const void* w_o2p;     /* packed obstacle_encoder[2].weight (obst_dim > 0) */
+    const float* b_o2;
+    const void* w_ffp;     /* the packed [H, H] blocks feed_forward[0].weight[zH:(z+1)H, pH:(p+1)H], contiguous in (z, p)
+                              order: z < 2, p < 1 + nbr_parts + (obst_dim > 0) in the order self, neighbour part(s),
+                              obstacle                                                                                   */
+    const float* b_ff;     /* [2H] */
+    const float* nbr;      /* [B, nbr_parts H] in, 16-byte aligned */
+    float* out;            /* [B, 2H] out */
+} qs_join_tower;
+/* obs: [B, obs_stride] rows.  self_dim 1..32 <= obs_stride; obst_dim 0..16 with 0 <= obst_off, obst_off + obst_dim <=
+ * obs_stride; nbr_parts 1 or 2; B >= 1.  The caller guarantees the split-f16 ranges: |obs| < 4094, |w| < 255.9 for every
+ * packed weight and |nbr| < 255.9 (the tokens: policy_fused bounds them by sqrt(H) max |ln_g| + max |ln_b|).  Asynchronous
+ * on `stream`. */
+int qs_encoder_join_x3(const float* d_obs, int32_t obs_stride, int32_t self_dim, int32_t obst_off, int32_t obst_dim,
+                       int32_t nbr_parts, int32_t B, int32_t H, const qs_join_tower* towers, int32_t n_towers, void* stream);
+
 /* The PPO update's MLP-family encoders (csrc/qs_policy_enc_train.h; new symbols, the ABI version is unchanged): what one
  * tower's forward saves and its backward reads and writes.  Every array is the caller's device memory; a branch the
  * policy does not have is not read and may be NULL. */

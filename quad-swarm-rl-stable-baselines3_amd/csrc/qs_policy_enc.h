@@ -25,6 +25,9 @@
 // table, 9 H floats.  H = 256: 135 168 + 9 216 B, one block per CU; H = 128: 69 632 + 4 608 B, two blocks per CU.
 // Registers at H = 256: accff 2 x 64, the working accumulator 64, the mean's sum 64 (NBR mean only), plus the weight
 // queue and the A operands of mfma_layer_x3 -- no scratch (DESIGN.md §4 has the resource-usage lines).
+//
+// At the end of the file: enc_join_x3_kernel, the same segment for the two attention families, whose neighbour part(s)
+// come from their own kernels' output rows instead of a branch here (qs_encoder_join_x3).
 #pragma once
 #include "qs_policy_x3.h"
 
@@ -218,6 +221,132 @@ __global__ __launch_bounds__(NTHR, H == 256 ? 1 : 2) void enc_mlp_x3_kernel(cons
                     const int n0 = acc_n0<H>(wave, c, g, lane);
                     st4g(t.out + (size_t)agent * (2 * H) + z * H + n0,
                          tanh_bias4(accff[z][rt][c], g, iSS, lds4(BI + (7 + z) * H + n0)));
+                }
+        }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The attention families' join (qs_encoder_join_x3): what follows their neighbour kernels up to the rows the tail reads.
+//   QuadMultiEncoder, neighbor_encoder_type "attention":  out = tanh([s | pooled | o] W_ff^T + b_ff)        NQ = 1
+//   QuadMultiHeadAttentionEncoder:                        out = tanh([s | token 0 | token 1] W_ff^T + b_ff)  NQ = 2
+// s and o are the self and obstacle branches of enc_mlp_x3_kernel (the same helpers, tiles and choreography); a
+// neighbour part is not computed here but staged: rows nbr[agent][qH .. (q + 1)H) (fp32, written by attn_pool_x3_kernel /
+// mha_encoder_x3_kernel) go through put4 at X3_SX into the tile that holds no part, then enc_ff.  Every part is at X3_SX,
+// so all of them accumulate into one accff at one scale; the tokens are LayerNorm outputs, bounded by the caller
+// (policy_fused: sqrt(H) max |ln_g| + max |ln_b| inside the f16 range at X3_SX).
+//
+// The row loads are the only HBM reads of activations on the block's path.  They are issued first, all NQ parts, 16 B per
+// lane and fully coalesced (a row is H / 4 consecutive lanes), and held in registers (NQ x 16 float4 per thread at H =
+// 256, NQ x 8 at 128) across the self branch: the memory counter retires in order, so the self gather's wait covers them
+// too and one HBM latency is paid per block instead of one per part.  The scheduling fences of the self branch's layers
+// keep the loads where they are written.  Registers at H = 256: accff 128 + acc 64 + the held rows 64 / 128 + the weight
+// queue, inside the 512 of one wave per SIMD -- no scratch.
+// LDS: the two alternating tiles and a 6 H float bias table: 135 168 + 6 144 B at H = 256 (one block per CU), 69 632 +
+// 3 072 B at H = 128 (two).
+struct JoinTowers {
+    qs_join_tower t[QS_ATTN_MAX_TOWERS];
+};
+
+template <int H>
+constexpr size_t join_lds_bytes() {
+    return (size_t)(4 * MROWS * GeoX3<H>::LDH) * 2 + (size_t)(6 * H) * 4;
+}
+
+template <int H>
+struct JoinRows {
+    static constexpr int NV = MROWS * (H / 4) / NTHR;
+    float4 v[NV];
+    // part q of the block's 64 agents; unconditional loads (row 0 stands in past B, zeroed by put's scale)
+    __device__ __forceinline__ void load(const float* __restrict__ nbr, int ldn, int q, int B, long row0, int tid) {
+#pragma unroll
+        for (int u = 0; u < NV; ++u) {
+            const int e = tid + u * NTHR, r = e / (H / 4), c4 = e - r * (H / 4);
+            v[u] = *reinterpret_cast<const float4*>(nbr + (row0 + r < B ? (size_t)(row0 + r) * ldn : 0) + q * H + 4 * c4);
+        }
+    }
+    __device__ __forceinline__ void put(const TileX3& P, int B, long row0, int tid) const {
+#pragma unroll
+        for (int u = 0; u < NV; ++u) {
+            const int e = tid + u * NTHR, r = e / (H / 4), c4 = e - r * (H / 4);
+            P.put4(r, 4 * c4, f4_scale(v[u], row0 + r < B ? X3_SX : 0.f));   // (exact: 2^8)
+        }
+    }
+};
+
+// raw observations and the neighbour kernels' rows -> the feed_forward output out [B, 2H] of one tower (blockIdx.y),
+// 64 agents per block.  NQ: neighbour parts (1 pooled row, 2 tokens); oo, od: the obstacle values' column and count.
+template <int H, int NQ>
+__global__ __launch_bounds__(NTHR, H == 256 ? 1 : 2) void enc_join_x3_kernel(const float* __restrict__ obs, int stride,
+                                                                            int so, int oo, int od, int B, JoinTowers tw) {
+    constexpr int LDH = GeoX3<H>::LDH, CT = Geo<H>::CT, TH = 2 * MROWS * LDH;
+    constexpr float iSS = 1.f / (X3_SX * X3_SW);
+    extern __shared__ float4 smem4[];
+    _Float16* th = reinterpret_cast<_Float16*>(smem4);
+    _Float16 *ta = th, *tb = th + TH;   // ta: the tile that holds no part (the next staging's, gather's and layer's target)
+    float* BI = reinterpret_cast<float*>(th + 2 * TH);   // b_s1, b_s2, b_o1, b_o2, b_ff [2H]
+    const qs_join_tower& t = tw.t[blockIdx.y];
+    const long row0 = (long)blockIdx.x * MROWS;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int NP = 1 + NQ + (od > 0 ? 1 : 0);
+
+    JoinRows<H> rows[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) rows[q].load(t.nbr, NQ * H, q, B, row0, tid);
+
+    for (int n = tid; n < H; n += NTHR) {
+        BI[n] = t.b_s1[n];
+        BI[H + n] = t.b_s2[n];
+        if (od > 0) {
+            BI[2 * H + n] = t.b_o1[n];
+            BI[3 * H + n] = t.b_o2[n];
+        }
+        BI[4 * H + n] = t.b_ff[n];
+        BI[5 * H + n] = t.b_ff[H + n];
+    }
+    auto swap = [&]() {
+        _Float16* x = ta;
+        ta = tb;
+        tb = x;
+    };
+
+    f32x16 acc[RT][CT], accff[2][RT][CT];
+    // self: the part ends in the gather's own tile
+    enc_gather0<ENC_SW>(enc_tile(ta, GeoX3<ENC_SW>::LDH), obs, stride, 0, so, B, row0, tid);
+    __syncthreads();
+    enc_layer0<H, ENC_SW>(ta, tb, t.w_s1p, BI, acc, wave, lane);
+    enc_layer<H>(tb, ta, t.w_s2p, BI + H, acc, wave, lane);
+    enc_ff<H, true>(ta, t.w_ffp, NP, 0, accff, wave, lane);
+    swap();
+
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {   // ta was last read before a barrier every wave has passed (enc_mlp_x3_kernel's order)
+        rows[q].put(enc_tile(ta, LDH), B, row0, tid);
+        __syncthreads();
+        enc_ff<H, false>(ta, t.w_ffp, NP, 1 + q, accff, wave, lane);
+        swap();
+    }
+    if (od > 0) {   // (uniform)
+        enc_gather0<ENC_OBW>(enc_tile(ta, GeoX3<ENC_OBW>::LDH), obs, stride, oo, od, B, row0, tid);
+        __syncthreads();
+        enc_layer0<H, ENC_OBW>(ta, tb, t.w_o1p, BI + 2 * H, acc, wave, lane);
+        enc_layer<H>(tb, ta, t.w_o2p, BI + 3 * H, acc, wave, lane);
+        enc_ff<H, false>(ta, t.w_ffp, NP, 1 + NQ, accff, wave, lane);
+    }
+
+    // out[agent][zH + n] = tanh(accff[z] + b_ff), 16-byte stores, rows < B
+#pragma unroll
+    for (int z = 0; z < 2; ++z)
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const long agent = row0 + acc_i(rt, lane);
+            if (agent >= B) continue;
+#pragma unroll
+            for (int c = 0; c < CT; ++c)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int n0 = acc_n0<H>(wave, c, g, lane);
+                    st4g(t.out + (size_t)agent * (2 * H) + z * H + n0,
+                         tanh_bias4(accff[z][rt][c], g, iSS, lds4(BI + (4 + z) * H + n0)));
                 }
         }
 }

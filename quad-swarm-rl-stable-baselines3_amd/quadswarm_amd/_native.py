@@ -204,6 +204,12 @@ class QsEncTower(ctypes.Structure):
                                                 "b_n3", "w_o1p", "b_o1", "w_o2p", "b_o2", "w_ffp", "b_ff", "out")]
 
 
+class QsJoinTower(ctypes.Structure):
+    """qs_join_tower (device pointers of one attention-family tower's join, quadswarm.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("w_s1p", "b_s1", "w_s2p", "b_s2", "w_o1p", "b_o1", "w_o2p", "b_o2", "w_ffp",
+                                                "b_ff", "nbr", "out")]
+
+
 ENC_NCOLMAX = 9           # qs_enc_train.colmax rows (QS_ENC_NCOLMAX)
 
 
@@ -277,7 +283,8 @@ EXPORTS = ["qs_abi_version", "qs_last_error", "qs_struct_sizes", "qs_config_defa
            "qs_tanh_grad_stats", "qs_linear_bias_x3", "qs_slab_sum_stats",
            "qs_linear_tanh_cat_x3", "qs_mha_encoder_x3", "qs_mha_encoder_train_x3", "qs_mha_bwd_x3", "qs_policy_tail_x3",
            "qs_policy_tail_train_x3", "qs_policy_tail_bwd_x3", "qs_encoder_mlp_x3",
-           "qs_encoder_mlp_train_x3", "qs_encoder_mlp_bwd_x3", "qs_dw_group_workspace", "qs_dw_group_x3"]
+           "qs_encoder_mlp_train_x3", "qs_encoder_mlp_bwd_x3", "qs_dw_group_workspace", "qs_dw_group_x3",
+           "qs_encoder_join_x3"]
 EXPORTS += ["qs_render_config_default", "qs_render_query", "qs_render"]
 EXPORTS += ["qs_shaping_config_default", "qs_shaping_workspace_bytes", "qs_shaping_enable", "qs_shaping_disable",
             "qs_shaping_buffers_get", "qs_shaping_set_training_steps"]
@@ -349,6 +356,7 @@ def lib():
                                   I32),
         "qs_dw_group_workspace": ([I32, I32, I32, P(SZ)], I32),
         "qs_dw_group_x3": ([P(QsDwJob), I32, I32, I32, V, SZ, V], I32),
+        "qs_encoder_join_x3": ([V, I32, I32, I32, I32, I32, I32, I32, P(QsJoinTower), I32, V], I32),
     }
     sig.update({
         "qs_render_config_default": ([P(QsRenderConfig)], I32),

@@ -26,6 +26,11 @@ tests/test_gpu_policy_encoder.py.
 tail="x3" (any family): everything after the feed_forward -- core, decoder, action_net / value_net, the squashed
 Gaussian's sampling and log-prob -- is one launch of qs_policy_tail_x3 (csrc/qs_policy_tail.h) for both towers in place
 of the torch row above.  tests/test_gpu_policy_tail.py.
+
+join="x3" (the two attention families, join_supports): the self encoder, the obstacle encoder and the feed_forward --
+what lies between the neighbour kernels and the tail -- are one launch of qs_encoder_join_x3 (csrc/qs_policy_enc.h
+enc_join_x3_kernel) for both towers, reading the neighbour kernels' rows in place; with tail "x3" a step of either
+family then issues no torch GEMM.  tests/test_gpu_policy_join.py.
 """
 import ctypes
 
@@ -43,6 +48,7 @@ def pack_mfma_weight(w):
 
 
 X3_SW = 256.0   # weight scale of the split-f16 packing (csrc/qs_policy_x3.h X3_SW)
+X3_SX = 256.0   # activation scale of the x3 tiles (csrc/qs_policy_x3.h X3_SX)
 X3_SIN = 16.0   # raw-observation scale of the x3 layer-0 inputs (csrc/qs_policy_x3.h X3_SIN)
 F16_MAX = 65504.0
 X3_SC = 16.0    # context scale of the multi-head attention encoder (csrc/qs_policy_mha.h X3_SC)
@@ -272,10 +278,11 @@ def enc_tower_biases(enc):
     return {k: v.detach().contiguous() for k, v in b.items()}
 
 
-def pack_enc_towers(encs):
+def pack_enc_towers(encs, tower_mats=enc_tower_mats, tower_biases=enc_tower_biases):
     """Every tower's qs_enc_tower operands: the matrices of enc_tower_mats packed in one pack_mfma_weights_x3 batch (the
-    feed_forward's blocks stacked, contiguous) plus the bias vectors.  ValueError for a weight out of the f16 range."""
-    mats = [enc_tower_mats(enc) for enc in encs]
+    feed_forward's blocks stacked, contiguous) plus the bias vectors.  ValueError for a weight out of the f16 range.
+    (tower_mats / tower_biases: the join's, pack_join_towers.)"""
+    mats = [tower_mats(enc) for enc in encs]
     flat, where = [], []
     for i, m in enumerate(mats):
         for name, w in m.items():
@@ -283,7 +290,7 @@ def pack_enc_towers(encs):
                 flat.append(w1)
                 where.append((i, name))
     pk = pack_mfma_weights_x3(flat)
-    out = [enc_tower_biases(enc) for enc in encs]
+    out = [tower_biases(enc) for enc in encs]
     for (i, name), t in zip(where, pk):
         if name == "w_ffp":
             out[i].setdefault(name, []).append(t)
@@ -292,6 +299,67 @@ def pack_enc_towers(encs):
     for w in out:
         w["w_ffp"] = torch.stack(w["w_ffp"]).contiguous()
     return out
+
+
+def _join_self(enc):
+    """The self branch of an attention-family encoder: QuadMultiEncoder's self_encoder, the multi-head family's
+    self_embed_layer."""
+    return enc.self_embed_layer if enc.cfg.encoder_type == "attention" else enc.self_encoder
+
+
+def join_supports(policy):
+    """Can qs_encoder_join_x3 (csrc/qs_policy_enc.h enc_join_x3_kernel) evaluate what follows this policy's neighbour
+    kernels -- self encoder, obstacle encoder, feed_forward -- in one launch?  A policy supports() accepts; tanh; rnn_size
+    128 or 256; the self encoder two Linear + Tanh of that width; the pooled neighbour row and the obstacle branch of that
+    width too (QuadMultiEncoder); self <= 32 and obstacle <= 16 columns."""
+    c = policy.cfg
+    if not supports(policy) or c.nonlinearity != "tanh" or c.rnn_size not in (128, 256):
+        return False
+    if not (1 <= c.self_obs_dim <= ENC_SW and 0 <= c.obstacle_obs_dim <= ENC_OBW):
+        return False
+    se = _join_self(policy.actor_encoder)
+    if not (len(se) == 4 and all(isinstance(se[i], torch.nn.Linear) and isinstance(se[i + 1], torch.nn.Tanh) and
+                                 se[i].out_features == c.rnn_size for i in (0, 2))):
+        return False
+    if c.encoder_type == "attention":   # [self | token 0 | token 1], the obstacle values inside the tokens
+        return True
+    return c.neighbor_hidden_size == c.rnn_size and (not c.obstacle_obs_dim or c.obst_hidden_size == c.rnn_size)
+
+
+def join_tower_mats(enc):
+    """enc_tower_mats for qs_join_tower: the self branch, the obstacle branch (QuadMultiEncoder with obstacles) and the
+    feed_forward's H x H blocks in (z, p) order over the parts [self | pooled | obstacle] or [self | token 0 | token 1]."""
+    if enc.cfg.encoder_type != "attention":
+        return enc_tower_mats(enc)   # (its neighbour kinds do not include attention: self, obstacle and blocks only)
+    H, se = enc.cfg.rnn_size, enc.self_embed_layer
+    w_s1 = torch.zeros(H, ENC_SW, dtype=torch.float32, device=se[0].weight.device)
+    w_s1[:, :se[0].in_features] = se[0].weight.detach()
+    wff = enc.feed_forward[0].weight
+    assert wff.shape == (2 * H, 3 * H)
+    return dict(w_s1p=w_s1, w_s2p=se[2].weight,
+                w_ffp=[wff[z * H:(z + 1) * H, p * H:(p + 1) * H] for z in range(2) for p in range(3)])
+
+
+def join_tower_biases(enc):
+    if enc.cfg.encoder_type != "attention":
+        return enc_tower_biases(enc)
+    se = enc.self_embed_layer
+    return {k: v.detach().contiguous() for k, v in dict(b_s1=se[0].bias, b_s2=se[2].bias, b_ff=enc.feed_forward[0].bias).items()}
+
+
+def pack_join_towers(encs):
+    """Every tower's qs_join_tower weights and biases: one pack_mfma_weights_x3 batch, one host read.  ValueError for a
+    weight out of the f16 range."""
+    return pack_enc_towers(encs, join_tower_mats, join_tower_biases)
+
+
+def join_token_bound(encs):
+    """max |token element| of the multi-head family: a LayerNorm output is at most sqrt(H) |ln_g| + |ln_b| (|x_hat| <
+    sqrt(H)).  One host read."""
+    lns = [enc.attention_layer.layer_norm for enc in encs]
+    g = torch.stack([ln.weight.detach().abs().amax() for ln in lns]).amax()
+    b = torch.stack([ln.bias.detach().abs().amax() for ln in lns]).amax()
+    return float(g * lns[0].normalized_shape[0] ** 0.5 + b)
 
 
 def tail_chain(core, decoder):
@@ -361,16 +429,30 @@ class FusedRolloutPolicy:
     PRECISIONS = ("fp32", "x3")
     TAILS = ("torch", "x3")
 
-    def __init__(self, policy, precision="fp32", tail="torch"):
+    JOINS = ("torch", "x3")
+
+    def __init__(self, policy, precision="fp32", tail="torch", join="torch"):
         """precision "fp32": fp32 operands on the fp32 matrix cores (v_mfma_f32_32x32x2f32); "x3": every fp32 product
         as three f16 products (hi/lo split, fp32 accumulation, ~7e-7 relative per product) on the f16 matrix cores
         (csrc/qs_policy_x3.h), 5.3x the contraction rate.
         tail "torch": core, decoder, heads and the action distribution as torch launches; "x3": as one launch of
-        qs_policy_tail_x3 (csrc/qs_policy_tail.h; the chain's products split like precision "x3", the heads fp32)."""
+        qs_policy_tail_x3 (csrc/qs_policy_tail.h; the chain's products split like precision "x3", the heads fp32).
+        join (the attention families, precision "x3"): what lies between the neighbour kernels and the tail -- self
+        encoder, obstacle encoder, feed_forward -- "torch": as torch and single-layer launches; "x3": as one launch of
+        qs_encoder_join_x3 (csrc/qs_policy_enc.h) that reads the neighbour kernels' rows in place."""
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision must be one of {self.PRECISIONS}")
         if tail not in self.TAILS:
             raise ValueError(f"tail must be one of {self.TAILS}")
+        if join not in self.JOINS:
+            raise ValueError(f"join must be one of {self.JOINS}")
+        if join == "x3" and not (precision == "x3" and join_supports(policy)):
+            raise ValueError("fused rollout join: needs precision 'x3' and a policy join_supports accepts (an attention "
+                             "family with tanh branches of width rnn_size 128 or 256)")
+        self.join_mode = join
+        self.packed_join = None        # what refresh() packed for the x3 join; None: the torch join evaluates
+        self.join_towers = (NAT.QsJoinTower * NAT.ATTN_MAX_TOWERS)()
+        self.join_out = None
         if tail == "x3" and not tail_supports(policy):
             raise ValueError("fused rollout tail: needs tanh core / decoder layers of width rnn_size (128 or 256), at "
                              "most 8 of them, and act_dim <= 8")
@@ -405,6 +487,8 @@ class FusedRolloutPolicy:
         towers are then packed (and evaluated) in fp32 until a later refresh finds every weight in range again."""
         if self.tail_mode == "x3":
             self._refresh_tail()
+        if self.join_mode == "x3":
+            self._refresh_join()
         if self.mha:
             return self._refresh_mha()
         if self.enc:
@@ -457,6 +541,8 @@ class FusedRolloutPolicy:
                 w_a3=att[4].weight.detach().reshape(-1).contiguous(), b_a3=float(att[4].bias.detach().item())))
             if prec == "x3" and H == 256:   # P = e_mean A_m^T + b_a1 on qs_linear_bias_x3 (|e_mean| <= 1)
                 packed[-1].update(w_a1mp=pack_linear_x3(att[0].weight[:, H:].detach()))
+            if self.packed_join is not None:   # the join kernel evaluates these layers: nothing to pack for the torch join
+                continue
             ff = enc.feed_forward[0]
             if prec == "x3" and ff_supported(ff) and float(ff.weight.detach().abs().amax()) < F16_MAX / X3_SW:
                 packed[-1].update(w_ffp=pack_linear_x3(ff.weight.detach()), b_ff=ff.bias.detach().contiguous())
@@ -511,7 +597,8 @@ class FusedRolloutPolicy:
         for enc in self.encs:
             w = pack_mha_tower(enc, H, nbw, od)
             se = enc.self_embed_layer
-            if self_l2_supported(se) and float(se[2].weight.detach().abs().amax()) < F16_MAX / X3_SW:
+            if (self.packed_join is None   # (else the join kernel evaluates the self encoder)
+                    and self_l2_supported(se) and float(se[2].weight.detach().abs().amax()) < F16_MAX / X3_SW):
                 w.update(w_s2p=pack_linear_x3(se[2].weight.detach()), b_s2=se[2].bias.detach().contiguous())
             packed.append(w)
         self.packed = packed
@@ -603,6 +690,53 @@ class FusedRolloutPolicy:
                                            self.cfg.obstacle_obs_dim, B, self.H, self.towers, len(self.encs), st),
                   "qs_encoder_mlp_x3")
         return self.out
+
+    # ---- the attention families' join: self encoder, obstacle encoder, feed_forward ----
+    def _refresh_join(self):
+        """Pack both towers for qs_encoder_join_x3.  A weight outside the split-f16 range (|w| >= 255.9), or LayerNorm
+        parameters that let a token reach it at the activation scale (sqrt(H) max |ln_g| + max |ln_b| >= 255.9), would
+        pack as +-inf: the torch join then evaluates until a later refresh finds everything in range again."""
+        import warnings
+        self.packed_join = None
+        lim = F16_MAX / X3_SX
+        if self.mha:
+            bound = join_token_bound(self.encs)
+            if not bound < lim:   # NaN fails too
+                warnings.warn(f"x3 rollout join: token bound sqrt(H) max |ln_g| + max |ln_b| = {bound:.4g} >= {lim:.4g}, "
+                              "outside the split-f16 range; evaluating in torch")
+                return
+        try:
+            packed = pack_join_towers(self.encs)
+        except ValueError as e:
+            warnings.warn(f"x3 rollout join: {e}; evaluating in torch")
+            return
+        for t, w in zip(self.join_towers, packed):
+            for name, x in w.items():
+                assert x.is_contiguous()
+                setattr(t, name, x.data_ptr())
+        self.packed_join = packed
+
+    def join_latents(self, obs, nbr, critic_only=False):
+        """[T, B, 2 rnn_size]: the towers' feed_forward outputs from the observations and the neighbour kernels' rows
+        nbr[i] ([B, H] pooled, or [B, 2H] tokens), read in place -- one launch of qs_encoder_join_x3 (critic_only: row 1
+        alone is computed).  The tensor is reused by the next call."""
+        B, T = obs.shape[0], len(self.encs)
+        parts = 2 if self.mha else 1
+        if self.join_out is None or self.join_out.shape[1] != B or self.join_out.device != obs.device:
+            self.join_out = torch.empty(T, B, 2 * self.H, dtype=torch.float32, device=obs.device)
+        for i in range(T):
+            x = nbr[i]
+            assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape == (B, parts * self.H)
+            self.join_towers[i].nbr, self.join_towers[i].out = x.data_ptr(), self.join_out[i].data_ptr()
+        if self.packed_precision != "x3":   # (else the neighbour kernels' call has taken the layer-0 range statistic)
+            m = obs.abs().amax()
+            self._obs_absmax = m if self._obs_absmax is None else torch.maximum(self._obs_absmax, m)
+        towers, n = (ctypes.pointer(self.join_towers[T - 1]), 1) if critic_only else (self.join_towers, T)
+        od = 0 if self.mha else self.cfg.obstacle_obs_dim   # the multi-head family's obstacle values are in its tokens
+        st = ctypes.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        NAT.check(self.L.qs_encoder_join_x3(ctypes.c_void_p(obs.data_ptr()), obs.shape[1], self.so, self.so + self.K * self.nd,
+                                            od, parts, B, self.H, towers, n, st), "qs_encoder_join_x3")
+        return self.join_out
 
     # ---- the tail: core, decoder, heads, action distribution ----
     def _refresh_tail(self):
@@ -742,6 +876,10 @@ class FusedRolloutPolicy:
             noise = None if deterministic else torch.randn((obs.shape[0], self.cfg.act_dim), device=obs.device)
             return self.tail(lat[0], lat[1], noise, deterministic)
         nbr = self.neighbor_encodings(obs)
+        if self.join_mode == "x3" and self.packed_join is not None:   # neighbour kernels, join, tail(): no torch GEMM
+            lat = self.join_latents(obs.contiguous(), nbr)
+            noise = None if deterministic else torch.randn((obs.shape[0], self.cfg.act_dim), device=obs.device)
+            return self.tail(lat[0], lat[1], noise, deterministic)
         if self.tail_mode == "x3":
             lat = [self._encode(enc, obs, nbr[i], self.packed[i]) for i, enc in enumerate(self.encs)]
             # (the draw of randn_like(mean) below: same generator, same shape)
@@ -765,6 +903,8 @@ class FusedRolloutPolicy:
         if self.enc:
             return self.tail(None, self.latents(obs)[1])[1]
         nbr = self.neighbor_encodings(obs)
+        if self.join_mode == "x3" and self.packed_join is not None:
+            return self.tail(None, self.join_latents(obs.contiguous(), nbr, critic_only=True)[1])[1]
         if self.tail_mode == "x3":
             return self.tail(None, self._encode(pol.critic_encoder, obs, nbr[1], self.packed[1]))[1]
         return pol.value_net(pol.critic_decoder(pol.critic_core(self._encode(pol.critic_encoder, obs, nbr[1],

@@ -591,9 +591,11 @@ class PPOTrainer:
     def __init__(self, env, policy: SwarmActorCritic, cfg: PPOConfig = None, device=None, seed=0,
                  gae_fn=None, group=None, fused_rollout=True, rollout_precision="fp32", update_precision="fp32",
                  mha_update="torch", rollout_tail="torch", update_tail="torch", rollout_encoder="torch",
-                 update_encoder="torch", update_dw="calls"):
+                 update_encoder="torch", update_dw="calls", rollout_join="torch"):
         import torch.distributed as dist
 
+        if rollout_join not in ("torch", "x3"):
+            raise ValueError("rollout_join must be 'torch' or 'x3'")
         if rollout_encoder not in ("torch", "x3"):
             raise ValueError("rollout_encoder must be 'torch' or 'x3'")
         if rollout_tail not in ("torch", "x3"):
@@ -642,10 +644,17 @@ class PPOTrainer:
         self.fused = None
         if rollout_tail == "x3" and self.device.type != "cuda":
             raise NAT.QuadSwarmError("rollout_tail='x3' needs a HIP device")
+        # rollout_join "x3" (the attention families): self encoder, obstacle encoder and feed_forward as one launch of
+        # qs_encoder_join_x3 between the neighbour kernels and the tail instead of torch and single-layer launches
+        if rollout_join == "x3":
+            from .policy_fused import join_supports
+            if not (self.device.type == "cuda" and fused_rollout and rollout_precision == "x3" and join_supports(policy)):
+                raise ValueError("rollout_join='x3' needs a HIP device, fused_rollout=True, rollout_precision='x3' and a "
+                                 "policy policy_fused.join_supports accepts")
         if fused_rollout and self.device.type == "cuda":
             from .policy_fused import FusedRolloutPolicy, supports
             if supports(policy):
-                self.fused = FusedRolloutPolicy(policy, precision=rollout_precision, tail=rollout_tail)
+                self.fused = FusedRolloutPolicy(policy, precision=rollout_precision, tail=rollout_tail, join=rollout_join)
         # rollout_encoder "x3": a QuadMultiEncoder with the mean_embed, mlp or no neighbour encoder from the observations
         # to its feed_forward output as one launch of qs_encoder_mlp_x3 per evaluation ("torch": these policies keep
         # fused None and the module evaluates them)

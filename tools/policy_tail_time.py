@@ -5,6 +5,10 @@ tail"); with --update, of the PPO update's tail (csrc/qs_policy_tail_train.h, PP
 autograd.
 
     python tools/policy_tail_time.py [--B 32768] [--iters 50] [--rounds 3] [--update [--envs 512] [--steps 8]] [--encoder]
+                                     [--join]
+
+--join: one rollout policy step of the two attention families (C3's and C4's policy shapes) with FusedRolloutPolicy(pol,
+"x3", tail="x3", join="x3") (csrc/qs_policy_enc.h enc_join_x3_kernel) against join="torch", and the joined segment alone.
 
 Two policies: C3's default (rnn_size 256, identity core, act_dim 4) and sb_train's (rnn_size 128, 6 core layers).  For
 each, mha_time.py's method (per round, alternating windows of `iters` back-to-back calls between two events, after
@@ -138,6 +142,38 @@ def encoder_mode(a):
             measure(fns, a, policy=name, B=a.B, R=pc.rnn_size, max_abs_diff_latents_vs_torch_fp32=diff)
 
 
+# --join: the attention families (csrc/qs_policy_enc.h enc_join_x3_kernel) at the C3 shape (the attention neighbour encoder)
+# and the C4 shape (the multi-head attention encoder), rnn_size 256, identity core
+JOIN_POLICIES = {"c3_attention": dict(self_obs_dim=18, neighbor_obs_dim=6, num_use_neighbor_obs=6, act_dim=4),
+                 "c4_mha": dict(self_obs_dim=19, neighbor_obs_dim=6, num_use_neighbor_obs=2, obstacle_obs_dim=9, act_dim=4,
+                                encoder_type="attention")}
+
+
+def join_mode(a):
+    """One rollout policy step of FusedRolloutPolicy(pol, "x3", tail="x3") with join "torch" against join "x3" (neighbour
+    kernels + qs_encoder_join_x3 + qs_policy_tail_x3), and the segment alone on fixed neighbour rows: the torch join's
+    launches against the one join launch."""
+    for name, kw in JOIN_POLICIES.items():
+        torch.manual_seed(0)
+        pc = PolicyConfig(**kw)
+        pol = SwarmActorCritic(pc).cuda().eval()
+        obs = torch.randn(a.B, pc.self_obs_dim + pc.neighbor_obs_dim * pc.num_use_neighbor_obs + pc.obstacle_obs_dim,
+                          device="cuda")
+        fps = {mode: FusedRolloutPolicy(pol, "x3", tail="x3", join=mode) for mode in ("torch", "x3")}
+        for fp in fps.values():
+            fp.refresh()
+            assert fp.packed_precision == "x3" and fp.packed_tail is not None
+        ft, fx = fps["torch"], fps["x3"]
+        assert fx.packed_join is not None
+        with torch.no_grad():
+            nbr = fx.neighbor_encodings(obs).clone()
+            fns = {"step_torch": lambda: ft(obs), "step_x3": lambda: fx(obs),
+                   "join_torch": lambda: [ft._encode(enc, obs, nbr[i], ft.packed[i]) for i, enc in enumerate(ft.encs)],
+                   "join_x3": lambda: fx.join_latents(obs, nbr)}
+            diff = max((x - y).abs().max().item() for x, y in zip(fns["join_x3"](), fns["join_torch"]()))
+            measure(fns, a, policy=name, B=a.B, R=pc.rnn_size, max_abs_diff_latents_vs_torch_join=diff)
+
+
 ENC_POLICIES_UPDATE = dict(ENC_POLICIES, c3_mean_embed=dict(self_obs_dim=18, neighbor_obs_dim=6, num_use_neighbor_obs=6,
                                                             act_dim=4, neighbor_encoder_type="mean_embed"))
 
@@ -208,7 +244,10 @@ def main():
     ap.add_argument("--update", action="store_true")
     ap.add_argument("--encoder", action="store_true")
     ap.add_argument("--dw", choices=("calls", "grouped"), default="calls")
+    ap.add_argument("--join", action="store_true")
     a = ap.parse_args()
+    if a.join:
+        return join_mode(a)
     if a.encoder and a.update:
         return update_encoder_mode(a)
     if a.encoder:
